@@ -1,8 +1,21 @@
 #!/usr/bin/env python3
 """bench.py — Mrays/s of the MI355X render core on BASELINE.json's headline workload.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config jumpy-1080p]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config jumpy-1080p] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run does what the headline figure needs and no more: it builds and commits the scene, counts the
+frame's rays with one untimed render, warms up, times the K steps, writes the last step's frame if
+`--dump-outputs DIR` is given and prints the result line (metric, value, unit, n_gpus, steps, warmup,
+ms_per_step, higher_is_better, dtype, config, paths_per_sec).  `--full` adds everything else described below
+to that line: the traversal counters and `roofline`, the path kernel's own HIP-event times, `multi_gpu`,
+`pcie_inclusive` (a second timed pass of K steps) and `cpu_baseline` (unless --no-cpu-baseline).
+
+`--dump-outputs DIR` writes DIR/frame.npy: the float32 frame (h x w x 3 radiance sums, rtw_render's layout) that the
+timed path left in rank 0's memory after its last timed step -- what a caller of that path receives.  A frame
+over 64 MB is written as a fixed sample of its pixels (k x 3, the pixels of a generator seeded with DUMP_SEED,
+in ascending raster order), the same pixels in every run.  Scene, camera and render seeds are constants, so two
+runs with the same arguments render the same frame and two builds compare output for output.
 
 `--gpus N` always means N GPUs.  Under a launcher (WORLD_SIZE set) it must equal WORLD_SIZE: one
 process per GPU, one RCCL all-gather.  Without a launcher and N > 1, this one process drives the N GPUs
@@ -68,6 +81,8 @@ CONFIGS = {
 }
 SCENE_SEED = 42      # replaces thread_rng() in scenes.rs
 RENDER_SEED = 2024
+DUMP_SEED = 7              # --dump-outputs: the pixel sample of a frame larger than DUMP_MAX_BYTES
+DUMP_MAX_BYTES = 64_000_000
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 FP32_PEAK_TFLOPS = 157.3   # MI355X_MICROARCH.md: peak FP32 vector (spec): v_fma_f32 at 32 lanes/clk/SIMD, 2 flops each
 # The issue ceiling of an exact-f32 kernel: compiled -ffp-contract=off and without packed math, every
@@ -219,6 +234,19 @@ def resolve_gpus(args, world: int, visible: int) -> int:
     return n
 
 
+def dump_outputs(out_dir: str, frame: np.ndarray) -> None:
+    """--dump-outputs: DIR/frame.npy, the last timed step's frame as float32 (whole, or a fixed seeded sample of
+    its pixels when it is larger than DUMP_MAX_BYTES)."""
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.nbytes > DUMP_MAX_BYTES:
+        px = frame.reshape(-1, 3)
+        keep = np.random.default_rng(DUMP_SEED).choice(len(px), size=DUMP_MAX_BYTES // 12, replace=False)
+        frame = px[np.sort(keep)]
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / "frame.npy", frame)
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None, help="GPUs to measure (default: WORLD_SIZE, else 1)")
@@ -227,9 +255,9 @@ def main() -> int:
     ap.add_argument("--config", default="jumpy-1080p", choices=sorted(CONFIGS))
     ap.add_argument("--spp", type=int, default=0, help="override spp (changes the workload!)")
     ap.add_argument("--launches", type=int, default=0, help="kernel launches per frame (0 = auto)")
-    ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU baseline work (3 runs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--traffic-json", default="", help="PMC HBM bytes per launch (from profiles/)")
+    ap.add_argument("--cpu-budget", type=float, default=12.0, help="--full: seconds of CPU baseline work (3 runs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--traffic-json", default="", help="--full: PMC HBM bytes per launch (from profiles/)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (default); gloo = CPU rehearsal of the N>1 path on one GPU")
     ap.add_argument("--check-image", action="store_true",
@@ -241,7 +269,15 @@ def main() -> int:
                     help="diagnostic (never a measurement): --multi-device N on ONE physical GPU, the scene's N "
                          "devices being logical ones (rtw_diag_alias_devices); needs RTW_RCCL_LIB pointing at an "
                          "RCCL stand-in that allows it (tests/loopback_rccl), as real RCCL refuses shared-GPU cliques")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the frame of the last timed step to DIR/frame.npy (float32; a fixed seeded pixel "
+                         "sample when the frame is over 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and print what the headline figure does not need: traversal counters and "
+                         "roofline, path-kernel event times, multi_gpu, pcie_inclusive, cpu_baseline")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit(f"--steps {args.steps} --warmup {args.warmup}: at least 1 step and 0 warm-up steps")
     if args.diag_alias and not (args.multi_device > 1 and os.environ.get("RTW_RCCL_LIB")):
         raise SystemExit("--diag-alias needs --multi-device N > 1 and RTW_RCCL_LIB set (tests/loopback_rccl)")
 
@@ -289,15 +325,18 @@ def main() -> int:
     else:
         all_ids = ids
     image = torch.zeros((h, w, 3), dtype=torch.float32, device=dev)
-    host_image = torch.empty((h, w, 3), dtype=torch.float32, pin_memory=True) if rank == 0 else None
+    # the pinned host frame of the PCIe-inclusive pass (--full)
+    host_image = torch.empty((h, w, 3), dtype=torch.float32, pin_memory=True) if rank == 0 and args.full else None
     stream = torch.cuda.current_stream()
 
     launches = args.launches or 1  # persistent path kernel: one launch drains the whole frame
     bounds = np.linspace(0, n_mine, launches + 1).astype(int)
 
     def render_frame():
+        nonlocal multi_frame
         if multi:
-            rt.render_multi(multi)  # blocking: renders, gathers over RCCL, copies the frame to the host
+            # blocking: renders, gathers over RCCL, copies the frame to the host
+            multi_frame, _ = rt.render_multi(multi)
             if timing_multi is not None:
                 timing_multi.append(scene.multi_times())
             return
@@ -345,9 +384,10 @@ def main() -> int:
     gev = None         # (start, end) events of the current step's all-gather (N > 1)
     gather_ev = []     # those of the timed steps
     timing_multi = None  # rtw_render_multi_times of the timed steps (single-process multi-device path)
-    # exact ray count + traversal counters of this rank's share (untimed, same seed => same work)
+    multi_frame = None   # the host frame rtw_render_multi returned last (single-process multi-device path)
+    # exact ray count of this rank's share (untimed, same seed => same work); --full: with the traversal counters
     st = rt.render_device(packed.data_ptr(), dev, ids.data_ptr(), n_mine, stream.cuda_stream,
-                          flags=rtw.FLAG_COUNT_TRAVERSAL, want_stats=True)
+                          flags=rtw.FLAG_COUNT_TRAVERSAL if args.full else 0, want_stats=True)
     counts = torch.tensor([st["rays"], st["node_visits"], st["boxes_tested"], n_mine * 64 * spp]
                           + st["prim_tests_by_type"], dtype=torch.float64, device=dev)
     rank_rays = [int(st["rays"])]
@@ -363,7 +403,7 @@ def main() -> int:
 
     for _ in range(args.warmup):
         render_frame()
-        frame_end(True)
+        frame_end(args.full)
     if args.check_image:  # the gathered frame must equal a single-device render, bit for bit
         render_frame()
         frame_end(False)
@@ -413,91 +453,115 @@ def main() -> int:
         return dt
 
     dt = timed(False, True)
-    # path_kernel alone: the library's HIP events around each launch on the launch stream, all K
-    # steps (a render call splits a frame larger than 2^32 paths into several passes, one launch each)
+    devs = range(multi) if multi else [dev]
     # every frame rendered so far is valid: no traversal guard tripped (raises otherwise)
-    for d in (range(multi) if multi else [dev]):
+    for d in devs:
         scene.render_status(d)
-    # every device's launches, read once (a read also forgets them: rtw_path_kernel_times)
-    pk_dev = {d: scene.path_kernel_times(d) for d in (range(multi) if multi else [dev])}
-    pk = pk_dev[0 if multi else dev]
-    if not pk or len(pk) >= 64 or len(pk) % (args.steps * launches):
-        raise SystemExit(f"path-kernel timings: got {len(pk)} for {args.steps} steps x {launches} calls "
-                         "(ring of 64 overflowed or launches missing; lower --steps)")
-    passes = len(pk) // (args.steps * launches)
-    frame_kernel_ms = float(sum(pk)) / args.steps
-    # the same K steps with rank 0 copying the frame to pinned host memory in each (PCIe-inclusive; never `value`)
-    dt_host = dt if multi else timed(True, False)
-    for d in (range(multi) if multi else [dev]):
-        scene.path_kernel_times(d)
-
+    frame = None
+    if args.dump_outputs and rank == 0:  # the last timed step's frame, taken before anything renders again
+        frame = multi_frame if multi else image.cpu().numpy()
     value = frame_rays * args.steps / dt / 1e6
-    # HBM bytes per launch from the committed rocprofv3 PMC summary of this config (FETCH_SIZE x2 +
-    # WRITE_SIZE, separate passes; scripts/gpu_r05_evidence.sh + scripts/summarize_round.py), if any --
-    # attached only when it was measured on THIS library build (its lib_sha stamp), else null + the reason
-    sha = rtw.lib_sha()
-    evidence_notes = []
 
-    def same_build(d, path):
-        if d.get("lib_sha") == sha:
-            return True
-        evidence_notes.append(f"{path.relative_to(ROOT)} was measured on build {d.get('lib_sha') or 'unstamped'}, "
-                              f"the timed library is {sha}: not attached")
-        return False
+    def full_figures():
+        """--full: the path kernel's own times over the timed steps, the PCIe-inclusive pass, roofline, multi_gpu."""
+        nonlocal timing_multi
+        # path_kernel alone: the library's HIP events around each launch on the launch stream, all K
+        # steps (a render call splits a frame larger than 2^32 paths into several passes, one launch each)
+        # every device's launches, read once (a read also forgets them: rtw_path_kernel_times)
+        pk_dev = {d: scene.path_kernel_times(d) for d in devs}
+        ksteps = args.steps  # the timed steps whose launches the library still holds
+        full_ring = any(len(v) >= 64 for v in pk_dev.values())
+        if world > 1:  # the extra frame below gathers: every rank renders it or none
+            f = torch.tensor([int(full_ring)], dtype=torch.int32, device=dev)
+            dist.all_reduce(f, op=dist.ReduceOp.MAX)
+            full_ring = bool(f.item())
+        if full_ring:
+            # more launches than the library's ring of 64 keeps: the kernel figures come from the last whole
+            # steps it holds; one untimed frame tells how many launches a step makes on each device
+            keep, timing_multi = timing_multi, None
+            render_frame()
+            frame_end(False)
+            torch.cuda.synchronize()
+            timing_multi = keep
+            per = {d: len(scene.path_kernel_times(d)) for d in devs}
+            if not all(0 < n < 64 for n in per.values()):
+                raise SystemExit(f"path-kernel timings: {per} launches per step do not fit the ring of 64")
+            ksteps = min([args.steps] + [63 // n for n in per.values()])
+            pk_dev = {d: pk_dev[d][-ksteps * per[d]:] for d in devs}
+        pk = pk_dev[0 if multi else dev]
+        if not pk or len(pk) % (ksteps * launches):
+            raise SystemExit(f"path-kernel timings: got {len(pk)} for {ksteps} steps x {launches} calls "
+                             "(launches missing)")
+        passes = len(pk) // (ksteps * launches)
+        frame_kernel_ms = float(sum(pk)) / ksteps
+        # the same K steps with rank 0 copying the frame to pinned host memory in each (PCIe-inclusive; never `value`)
+        dt_host = dt if multi else timed(True, False)
+        for d in devs:
+            scene.path_kernel_times(d)
 
-    traffic, traffic_src = None, None
-    tj = Path(args.traffic_json) if args.traffic_json else ROOT / "profiles" / f"pmc_{args.config}.json"
-    if tj.exists() and not args.spp and not multi:
-        d = json.loads(tj.read_text())
-        if d.get("launches_per_frame", 1) == launches and d.get("world", 1) == world and same_build(d, tj):
-            traffic, traffic_src = d.get("hbm_bytes_per_launch"), str(tj.relative_to(ROOT))
-    # what bounds it: SQ counters of the same config and build (summarize_round.py)
-    issue = None
-    vj = ROOT / "profiles" / f"valu_{args.config}.json"
-    if vj.exists() and not args.spp and not multi:
-        d = json.loads(vj.read_text())
-        if same_build(d, vj):
-            issue = {k: d.get(k) for k in ("valu_busy", "valu_lane_util", "wave_wait", "wave_issue", "l2_hit",
-                                            "ta_busy", "td_busy", "lds_active", "lds_conflict_share",
-                                            "tcp_hit", "vmem_rd_per_ray")}
-            issue["source"] = str(vj.relative_to(ROOT))
-    multi_gpu = None
-    if world > 1:  # per-rank kernel / gather time: imbalance vs gather cost (a scaling run's diagnosis)
-        gms = sum(a.elapsed_time(b) for a, b in gather_ev) / len(gather_ev) if gather_ev else float("nan")
-        mine_t = torch.tensor([frame_kernel_ms, gms], dtype=torch.float64, device=dev)
-        allt = [torch.zeros_like(mine_t) for _ in range(world)]
-        dist.all_gather(allt, mine_t)
-        km = [round(float(x[0].item()), 3) for x in allt]
-        gm = [round(float(x[1].item()), 3) for x in allt]
-        multi_gpu = {"rank_kernel_ms_per_frame": km, "rank_gather_ms_per_frame": gm, "rank_rays_per_frame": rank_rays,
-                     "kernel_imbalance_max_over_min": round(max(km) / min(km), 4) if min(km) > 0 else None,
-                     "gather_ms_min_over_ranks": min(gm),
-                     "note": "gather ms = all-gather on torch's stream, incl. waiting for the slowest rank; its "
-                             "minimum over ranks (the slowest rank's) is the transfer cost"}
-    if multi and timing_multi:  # the same diagnosis for the single-process N-GPU path (rtw_render_multi)
-        dms = np.array([t[0] for t in timing_multi], dtype=np.float64)  # steps x devices
-        gms_m = float(np.mean([t[1] for t in timing_multi]))
-        dk = []  # path-kernel ms per frame of every device (the library's events on that device's stream)
-        for d in range(multi):
-            pkd = pk_dev[d]
-            dk.append(round(float(sum(pkd)) / args.steps, 3) if pkd else None)
-        km = [round(float(x), 3) for x in dms.mean(axis=0)]
-        multi_gpu = {"device_kernel_ms_per_frame": dk, "device_render_ms_per_frame": km,
-                     "gather_ms_per_frame": round(gms_m, 3),
-                     "kernel_imbalance_max_over_min": round(max(km) / min(km), 4) if min(km) > 0 else None,
-                     "note": "render ms = path kernel + in-order reduction per device (HIP events on its stream); "
-                             "gather ms = device 0's stream from the end of its render to the last device's "
-                             "tiles (RCCL send/recv group), so it includes waiting for the slowest device"}
-    n_launch = launches * passes
-    # per launch of this rank (multi-device: device 0's launches, its 1/N share of the frame)
-    roof = roofline(cnt, frame_kernel_ms / n_launch, n_launch, multi or world, traffic, issue)
+        # HBM bytes per launch from the committed rocprofv3 PMC summary of this config (FETCH_SIZE x2 +
+        # WRITE_SIZE, separate passes; scripts/gpu_r05_evidence.sh + scripts/summarize_round.py), if any --
+        # attached only when it was measured on THIS library build (its lib_sha stamp), else null + the reason
+        sha = rtw.lib_sha()
+        evidence_notes = []
 
-    out = None
-    if rank == 0:
-        n_dev = multi or world
+        def same_build(d, path):
+            if d.get("lib_sha") == sha:
+                return True
+            evidence_notes.append(f"{path.relative_to(ROOT)} was measured on build {d.get('lib_sha') or 'unstamped'}, "
+                                  f"the timed library is {sha}: not attached")
+            return False
+
+        traffic, traffic_src = None, None
+        tj = Path(args.traffic_json) if args.traffic_json else ROOT / "profiles" / f"pmc_{args.config}.json"
+        if tj.exists() and not args.spp and not multi:
+            d = json.loads(tj.read_text())
+            if d.get("launches_per_frame", 1) == launches and d.get("world", 1) == world and same_build(d, tj):
+                traffic, traffic_src = d.get("hbm_bytes_per_launch"), str(tj.relative_to(ROOT))
+        # what bounds it: SQ counters of the same config and build (summarize_round.py)
+        issue = None
+        vj = ROOT / "profiles" / f"valu_{args.config}.json"
+        if vj.exists() and not args.spp and not multi:
+            d = json.loads(vj.read_text())
+            if same_build(d, vj):
+                issue = {k: d.get(k) for k in ("valu_busy", "valu_lane_util", "wave_wait", "wave_issue", "l2_hit",
+                                                "ta_busy", "td_busy", "lds_active", "lds_conflict_share",
+                                                "tcp_hit", "vmem_rd_per_ray")}
+                issue["source"] = str(vj.relative_to(ROOT))
+        multi_gpu = None
+        if world > 1:  # per-rank kernel / gather time: imbalance vs gather cost (a scaling run's diagnosis)
+            gms = sum(a.elapsed_time(b) for a, b in gather_ev) / len(gather_ev) if gather_ev else float("nan")
+            mine_t = torch.tensor([frame_kernel_ms, gms], dtype=torch.float64, device=dev)
+            allt = [torch.zeros_like(mine_t) for _ in range(world)]
+            dist.all_gather(allt, mine_t)
+            km = [round(float(x[0].item()), 3) for x in allt]
+            gm = [round(float(x[1].item()), 3) for x in allt]
+            multi_gpu = {"rank_kernel_ms_per_frame": km, "rank_gather_ms_per_frame": gm, "rank_rays_per_frame": rank_rays,
+                         "kernel_imbalance_max_over_min": round(max(km) / min(km), 4) if min(km) > 0 else None,
+                         "gather_ms_min_over_ranks": min(gm),
+                         "note": "gather ms = all-gather on torch's stream, incl. waiting for the slowest rank; its "
+                                 "minimum over ranks (the slowest rank's) is the transfer cost"}
+        if multi and timing_multi:  # the same diagnosis for the single-process N-GPU path (rtw_render_multi)
+            dms = np.array([t[0] for t in timing_multi], dtype=np.float64)  # steps x devices
+            gms_m = float(np.mean([t[1] for t in timing_multi]))
+            dk = []  # path-kernel ms per frame of every device (the library's events on that device's stream)
+            for d in range(multi):
+                pkd = pk_dev[d]
+                dk.append(round(float(sum(pkd)) / ksteps, 3) if pkd else None)
+            km = [round(float(x), 3) for x in dms.mean(axis=0)]
+            multi_gpu = {"device_kernel_ms_per_frame": dk, "device_render_ms_per_frame": km,
+                         "gather_ms_per_frame": round(gms_m, 3),
+                         "kernel_imbalance_max_over_min": round(max(km) / min(km), 4) if min(km) > 0 else None,
+                         "note": "render ms = path kernel + in-order reduction per device (HIP events on its stream); "
+                                 "gather ms = device 0's stream from the end of its render to the last device's "
+                                 "tiles (RCCL send/recv group), so it includes waiting for the slowest device"}
+        n_launch = launches * passes
+        # per launch of this rank (multi-device: device 0's launches, its 1/N share of the frame)
+        roof = roofline(cnt, frame_kernel_ms / n_launch, n_launch, multi or world, traffic, issue)
         roof.update({"traffic_source": traffic_src, "issue_counters": issue, "lib_sha": sha,
                      "evidence_notes": evidence_notes or None, "kernel": "path_kernel",
                      "kernel_ms_per_frame": round(frame_kernel_ms, 3), "kernel_launches_per_frame": n_launch,
+                     "kernel_steps_measured": ksteps,
                      "node_fetches_per_ray": round(cnt["node4"] / max(1, cnt["rays"]), 3),
                      "boxes_per_ray": round(cnt["boxes"] / max(1, cnt["rays"]), 3),
                      "prim_tests_per_ray": round(float(cnt["prims"].sum()) / max(1, cnt["rays"]), 3),
@@ -505,6 +569,17 @@ def main() -> int:
                                 "boxes": int(cnt["boxes"]), "prims_by_type": [int(x) for x in cnt["prims"]]},
                      "simd_util_rank0": {k: (round(v, 3) if v else v) for k, v in st["simd_util"].items()},
                      "phase_share_rank0": {k: (round(v, 3) if v else v) for k, v in st["phase_share"].items()}})
+        return roof, multi_gpu, dt_host
+
+    if args.full:
+        roof, multi_gpu, dt_host = full_figures()
+    else:  # nothing else reads the library's launch events: forget them
+        for d in devs:
+            scene.path_kernel_times(d)
+
+    out = None
+    if rank == 0:
+        n_dev = multi or world
         out = {
             "metric": "Mrays/sec at 1920x1080, 512 spp, 50 bounces; 1/2/4/8-GPU scaling",
             "value": round(value, 2),
@@ -524,21 +599,25 @@ def main() -> int:
                        "rays_per_frame": frame_rays, "paths_per_frame": w * h * spp, "tiles": nt,
                        "launches_per_frame": launches,
                        "parallelism": f"tiles{n_dev}" + ("-single-process" if multi else "")},
-            "roofline": roof,
             "paths_per_sec": round(w * h * spp * args.steps / dt, 1),
-            "pcie_inclusive": {"value": round(frame_rays * args.steps / dt_host / 1e6, 2),
-                               "ms_per_step": round(dt_host / args.steps * 1e3, 3),
-                               "note": "the same K steps with rank 0 copying the frame (w x h x 3 f32) to pinned host "
-                                       "memory in each: the rate through rtw_render's host-buffer boundary"},
+            "full": args.full,
         }
-        if multi_gpu:
-            out["multi_gpu"] = multi_gpu
         if out["n_gpus"] != args.gpus:  # never print an N = 1 line for an N-GPU request
             raise SystemExit(f"bench measured {out['n_gpus']} GPU(s) but --gpus {args.gpus} was requested")
-        if n_dev == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(scene, cam, bg, w, h, spp, args.cpu_budget)
-        else:
-            out["cpu_baseline"] = None
+        if frame is not None:
+            dump_outputs(args.dump_outputs, frame)
+        if args.full:
+            out["roofline"] = roof
+            out["pcie_inclusive"] = {"value": round(frame_rays * args.steps / dt_host / 1e6, 2),
+                                     "ms_per_step": round(dt_host / args.steps * 1e3, 3),
+                                     "note": "the same K steps with rank 0 copying the frame (w x h x 3 f32) to pinned "
+                                             "host memory in each: the rate through rtw_render's host-buffer boundary"}
+            if multi_gpu:
+                out["multi_gpu"] = multi_gpu
+            if n_dev == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(scene, cam, bg, w, h, spp, args.cpu_budget)
+            else:
+                out["cpu_baseline"] = None
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

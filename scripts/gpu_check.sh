@@ -2,11 +2,12 @@
 set -o pipefail
 cd $GRAFT_REPO_ROOT
 TAG=${TAG:-r1_}
-mkdir -p gpurun_out
-(nproc; rocm-smi --showproductname 2>&1 | head -20) > gpurun_out/${TAG}info.txt || true
-timeout -k 10 400 python -m pytest tests -m gpu -x -q > gpurun_out/${TAG}pytest.log 2>&1
-rc=$?; echo "pytest rc=$rc" >> gpurun_out/${TAG}pytest.log; tail -5 gpurun_out/${TAG}pytest.log
+O=${OUT:-out}  # where the logs go
+mkdir -p $O
+(nproc; rocm-smi --showproductname 2>&1 | head -20) > $O/${TAG}info.txt || true
+timeout -k 10 400 python -m pytest tests -m gpu -x -q > $O/${TAG}pytest.log 2>&1
+rc=$?; echo "pytest rc=$rc" >> $O/${TAG}pytest.log; tail -5 $O/${TAG}pytest.log
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 400 python bench.py ${BENCH_ARGS} > gpurun_out/${TAG}bench.log 2>&1
-rc=$?; echo "bench rc=$rc"; tail -2 gpurun_out/${TAG}bench.log
+timeout -k 10 400 python bench.py --full ${BENCH_ARGS} > $O/${TAG}bench.log 2>&1
+rc=$?; echo "bench rc=$rc"; tail -2 $O/${TAG}bench.log
 exit $rc

@@ -35,9 +35,9 @@ cd /tmp && export TMPDIR=/tmp
 for c in ${CONFIGS:-jumpy-1080p cornell-800 cow-1080p monument-4k}; do
   O=$R/gpurun_out/${TAG}$c
   mkdir -p $O
-  timeout -k 10 300 python3 $R/bench.py --config $c --steps 3 --warmup 1 > $O/bench.log 2>&1 || { tail -5 $O/bench.log; exit 1; }
+  timeout -k 10 300 python3 $R/bench.py --config $c --steps 3 --warmup 1 --full > $O/bench.log 2>&1 || { tail -5 $O/bench.log; exit 1; }
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o kt -- \
-    python3 $R/bench.py --config $c --steps 2 --warmup 1 --no-cpu-baseline > $O/kt.log 2>&1 || { tail -5 $O/kt.log; exit 1; }
+    python3 $R/bench.py --config $c --steps 2 --warmup 1 --full --no-cpu-baseline > $O/kt.log 2>&1 || { tail -5 $O/kt.log; exit 1; }
   for p in FETCH_SIZE WRITE_SIZE; do
     timeout -k 10 300 rocprofv3 --pmc $p --kernel-trace --output-format csv --kernel-include-regex "path_kernel|reduce_kernel" \
       -d $O/pmc_$p -o pmc -- python3 $R/bench.py --config $c --steps 1 --warmup 0 --no-cpu-baseline > $O/pmc_$p.log 2>&1 || { tail -5 $O/pmc_$p.log; exit 1; }

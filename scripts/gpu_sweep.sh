@@ -2,9 +2,11 @@
 set -o pipefail
 cd $GRAFT_REPO_ROOT
 TAG=${TAG:-sw_}
-timeout -k 10 300 python -m pytest tests -m gpu -x -q > gpurun_out/${TAG}pytest.log 2>&1 || { tail -20 gpurun_out/${TAG}pytest.log; exit 1; }
-tail -1 gpurun_out/${TAG}pytest.log
+O=${OUT:-out}  # where the logs go
+mkdir -p $O
+timeout -k 10 300 python -m pytest tests -m gpu -x -q > $O/${TAG}pytest.log 2>&1 || { tail -20 $O/${TAG}pytest.log; exit 1; }
+tail -1 $O/${TAG}pytest.log
 for kv in $SWEEP; do
-  env $kv timeout -k 10 200 python bench.py --steps 3 --warmup 1 --no-cpu-baseline $BENCH_ARGS > gpurun_out/${TAG}$kv.log 2>&1 || exit $?
-  echo "$kv $(grep -o '"value": [0-9.]*' gpurun_out/${TAG}$kv.log) $(grep -o '"simd_util_rank0": {[^}]*}' gpurun_out/${TAG}$kv.log) $(grep -o '"phase_share_rank0": {[^}]*}' gpurun_out/${TAG}$kv.log)"
+  env $kv timeout -k 10 200 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline $BENCH_ARGS > $O/${TAG}$kv.log 2>&1 || exit $?
+  echo "$kv $(grep -o '"value": [0-9.]*' $O/${TAG}$kv.log) $(grep -o '"simd_util_rank0": {[^}]*}' $O/${TAG}$kv.log) $(grep -o '"phase_share_rank0": {[^}]*}' $O/${TAG}$kv.log)"
 done

@@ -7,9 +7,10 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-REF_MODELS = Path("/root/reference/models")
-
 ROOT = Path(__file__).resolve().parents[1]
+# Normals_Try3.obj here is the head of the reference's mesh of that name: its header, the first 14 `v` and `vt` and
+# 8 `vn` lines, and its first group's `g` / `usemtl` / `s` lines with the first four faces (the file has no `mtllib`)
+REF_MODELS = ROOT / "tests" / "golden" / "models"
 
 
 def header_functions():
@@ -118,7 +119,6 @@ def test_presets_unknown_scene(rtw):
     assert "unknown" in str(e.value)
 
 
-@pytest.mark.skipif(not (REF_MODELS / "Normals_Try3.obj").exists(), reason="reference models not mounted")
 def test_suspension_obj_fails_like_the_reference(rtw):
     """scenes.rs:773-814 loads Normals_Try3.obj, whose `usemtl` has no `mtllib`: the reference
     panics at triangular.rs:176 (unwrap); the preset returns RTW_EIO."""

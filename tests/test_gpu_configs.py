@@ -60,6 +60,39 @@ def test_config0_console_png(gpu, tmp_path):
     assert np.array_equal(got, want), f"{int((got != want).sum())} bytes differ"
 
 
+def test_bench_plain_run_dumps_the_timed_frame(gpu, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` prints the headline line only (what --full adds is absent),
+    with the K it was given and a positive ms_per_step, and --dump-outputs writes the frame of its last timed
+    step: configs[0]'s frame, bit for bit the one rtw_render returns for bench.py's scene and seeds."""
+    import json
+    import sys
+    rtw = gpu
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--config", "jumpy-400", "--steps", "3",
+                        "--warmup", "1", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = lines[0]
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["full"] is False
+    assert d["unit"] == "Mrays/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["ms_per_step"] > 0 and d["value"] > 0
+    # value = rays per frame / step time; the line rounds ms_per_step to 0.001 ms and value to 0.01
+    rate = d["config"]["rays_per_frame"] / d["ms_per_step"] / 1e3
+    assert abs(d["value"] - rate) <= rate * 0.001 / d["ms_per_step"] + 0.01
+    for k in ("roofline", "pcie_inclusive", "cpu_baseline", "multi_gpu"):
+        assert k not in d, k
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == ["frame.npy"]
+    got = np.load(tmp_path / "out" / "frame.npy")
+    assert got.dtype == np.float32 and got.shape == (225, 400, 3)
+    s = rtw.Scene()
+    cam, bg = s.preset("jumpy-balls", rtw.camera_aspect(400, 225), seed=SCENE_SEED)
+    s.commit(device=0)
+    want, st = rtw.Raytracer(s, cam, bg, 400, 225, 50, seed=RENDER_SEED).render()
+    assert d["config"]["rays_per_frame"] == st["rays"]
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+
+
 def _sphere_cloud(rtw, n=200, seed=4):
     """Spheres of one size (no always-tested prim: every ray goes through the BVH walk)."""
     rng = np.random.default_rng(seed)

@@ -118,7 +118,7 @@ def test_bench_multi_device_branch_runs(gpu):
     root = Path(__file__).resolve().parents[1]
     env = dict(os.environ, RTW_RCCL_LIB=str(LOOPBACK))
     r = subprocess.run([sys.executable, str(root / "bench.py"), "--multi-device", "8", "--diag-alias", "--config",
-                        "monument-4k", "--spp", "1", "--steps", "2", "--warmup", "1", "--check-image",
+                        "monument-4k", "--spp", "1", "--steps", "2", "--warmup", "1", "--check-image", "--full",
                         "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]

@@ -208,6 +208,25 @@ def test_bench_gpus_routing_under_launcher():
             b.resolve_gpus(_args(**kw), world=4, visible=8)
 
 
+def test_bench_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: a frame within the size limit is written whole as float32; a larger one as the same
+    seeded sample of its pixels (ascending raster order) in every run, within the limit."""
+    b = _bench_module()
+    frame = np.arange(5 * 7 * 3, dtype=np.float32).reshape(5, 7, 3)
+    b.dump_outputs(str(tmp_path / "a"), frame)
+    got = np.load(tmp_path / "a" / "frame.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, frame)
+    monkeypatch.setattr(b, "DUMP_MAX_BYTES", 12 * 9)  # room for 9 of the 35 pixels
+    b.dump_outputs(str(tmp_path / "b"), frame)
+    b.dump_outputs(str(tmp_path / "c"), frame)
+    s1, s2 = np.load(tmp_path / "b" / "frame.npy"), np.load(tmp_path / "c" / "frame.npy")
+    assert s1.dtype == np.float32 and s1.shape == (9, 3) and s1.nbytes <= 12 * 9
+    assert np.array_equal(s1, s2)
+    px = frame.reshape(-1, 3)
+    idx = (s1[:, 0] / 3).astype(int)  # pixel p holds 3p, 3p + 1, 3p + 2
+    assert np.array_equal(px[idx], s1) and np.all(np.diff(idx) > 0)
+
+
 def test_bench_gpus_2_without_gpus_fails_loudly():
     """`python bench.py --gpus 2` on a box without 2 visible GPUs (here: none) exits non-zero and prints no
     bench line -- never a 1-GPU number for a 2-GPU request."""
