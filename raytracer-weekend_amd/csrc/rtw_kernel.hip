@@ -2013,7 +2013,9 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(OCC, 8))) v
               pool_end = b < P ? (b + batch < P ? b + batch : P) : P;
             }
           }
-          if (pool_next < pool_end) {  // pools and passes hold whole multiples of 64 ids
+          // pools and passes hold whole multiples of 64 ids: the host rounds every batch size to one (batch_ids in
+          // enqueue_render; the automatic halving stays on powers of two >= 128) and n_paths = slots x 64 x spp
+          if (pool_next < pool_end) {
             const uint64_t id = pool_next + lane;
             PathState g;
             const bool ok = start_path<SLDS, 0, 0, AB>(SA, id, g);
@@ -2088,11 +2090,13 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(OCC, 8))) v
       }
       if (lane == 0) { pool[0] = pool_next; pool[1] = pool_end; }
     }
+    // (before the empty-round exits: a round that starts no path, a wave's last one included, is regeneration time
+    // too; marked after them it fell to shading, and the path_start share could exceed regeneration's)
+    phase(0);
     if (__ballot(has) == 0) {
       if (exhausted) break;
       continue;  // every id handed out this round was an off-image pixel: draw again
     }
-    phase(0);
     // segments starting now, counted per wave with every lane active (so the count is uniform
     // and stays in SGPRs)
     nrays += (unsigned long long)__popcll(__ballot(has && !ts.on));
@@ -2712,6 +2716,11 @@ static float recip_rn(float b) {
   return best;
 }
 
+// A batch size (knob RTW_BATCH) as the kernels take it: within [64, 65536] and rounded down to a multiple of 64.
+// Passes hold 64 x spp ids per slot, so every batch of a pass, its last one included, is then whole groups of 64
+// consecutive ids: path_kernel's start ring (SRING) builds 64 starts from pool_next + lane without a bound check.
+static uint32_t batch_ids(int v) { return (uint32_t)std::min(65536, std::max(64, v)) & ~63u; }
+
 int check_guard(DeviceCopy& c) {
   volatile uint32_t* e = c.err_host;
   if (e && *e) {
@@ -2766,7 +2775,8 @@ int enqueue_render(Scene& sc, DeviceCopy& c, const rtw_camera* cam, const float 
   a.tile_stride = ts.stride;
   a.packed_out = (d_tiles || ts.packed) ? 1u : 0u;
   a.err = c.err_host;
-  a.batch = (uint32_t)std::min(65536, std::max(64, env_int("RTW_BATCH", (int)dev::BATCH)));
+  // whole wave-loads of ids only (batch_ids): the start ring makes 64 path starts from 64 consecutive ids of a batch
+  a.batch = batch_ids(env_int("RTW_BATCH", (int)dev::BATCH));
   a.quota16 = 12;  // see trace_run (measured best of 4..16 on jumpy-balls); tuning knob RTW_QUOTA16 (1..16)
   if (const char* q = tuning_env("RTW_QUOTA16")) a.quota16 = (uint32_t)std::min(16, std::max(1, atoi(q)));
   // test postponed leaves once leaf16/16 of the wave's lanes hold one and cannot descend (trace_run);
@@ -2808,7 +2818,7 @@ int enqueue_render(Scene& sc, DeviceCopy& c, const rtw_camera* cam, const float 
     // tail; jumpy-1080p +1.2%, cornell-800 +0.5% over 2048, profiles/r03/experiments k3 / k4); the mesh
     // kernels keep 2048 (neutral on cow; their short paths made small batches costly in round 2)
     if ((var.k16 && var.block == 1024u) || sc.flat.nodes4.empty())
-      a.batch = (uint32_t)std::min(65536, std::max(64, env_int("RTW_BATCH", 1024)));
+      a.batch = batch_ids(env_int("RTW_BATCH", 1024));
     // Regenerate paths only once >= regen_min lanes of a wave are idle (or all are): start_path
     // runs at wave level, so batching it raises its SIMD utilisation.  Measured on MI355X
     // (RTW_REGEN_MIN sweep 1..32): 24 is best for open scenes (jumpy-balls +4.3%, cow +1.6%,

@@ -144,7 +144,7 @@ def test_stack_spill_bit_exact(gpu, orc, knobs, name, aspect, w, h, spp):
                                   "RTW_HALF_NODES=0", "RTW_TRI_LEAF=0", "RTW_LDSN_WAVES=6", "RTW_LDSN_WAVES=7",
                                   "RTW_LDSN_BLK=512", "RTW_MESH_S16=0", "RTW_MESH_S16=6",
                                   "RTW_MESH_S16=7", "RTW_BVH_PAIR=1", "RTW_BVH_BINS=64", "RTW_BATCH=64",
-                                  "RTW_BATCH=65536"])
+                                  "RTW_BATCH=65536", "RTW_BATCH=100", "RTW_BATCH=1000"])
 def test_scheduling_knobs_bit_exact(gpu, orc, knobs, knob):
     """When a wave regenerates paths (RenderArgs::regen_min) and when a suspended traversal
     yields (quota16) change only which lanes run which path when; every path's draws and
@@ -155,7 +155,8 @@ def test_scheduling_knobs_bit_exact(gpu, orc, knobs, knob):
     whatever culls them -- with one documented exemption: RTW_LIST_MAX=0 walks a list world's rects
     through a BVH, whose fold counts a NaN candidate (an in-plane bounce, t = 0/0) as a miss where the reference's
     list order lets it win; these frames hold no in-plane bounce (cornell-800 x 32 holds two, pinned in list mode by
-    test_in_plane_bounce_list_mode)."""
+    test_in_plane_bounce_list_mode).  RTW_BATCH values that are no multiple of 64 (100, 1000) are rounded down to one
+    by the host (64, 960): the start ring takes 64 consecutive ids of a batch at a time."""
     k, v = knob.split("=")
     knobs.setenv(k, v)
     # the half-node knobs matter for BVH worlds: jumpy-balls (LDS nodes) and the cow (global nodes)
@@ -211,6 +212,39 @@ def test_start_ring_passes_and_tiles(gpu, knobs):
             rtw.unpack_tiles_device(w, h, ids.data_ptr(), len(ids), packed.data_ptr(), img.data_ptr(), 0,
                                     torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
+        assert np.array_equal(img.cpu().numpy().view(np.uint32), full.view(np.uint32)), world
+
+
+def test_start_ring_batch_not_a_multiple_of_64(gpu, knobs):
+    """RTW_BATCH=100 over the ragged frame of test_start_ring_passes_and_tiles, as packed tiles for world sizes 1, 2
+    and 5: here a pass's last batch is short and tile_ids is a real, short table, and the ring builds 64 starts from
+    ids pool_next + lane without looking at the pool's end.  The host rounds the batch down to a multiple of 64
+    (enqueue_render), so no ring reaches into another wave's batch (those paths would be rendered twice: more rays)
+    or past the pass (ids beyond tile_ids).  Bits and rays equal the default-batch full frame's."""
+    torch = pytest.importorskip("torch")
+    rtw = gpu
+    s = rtw.Scene()
+    cam, bg = s.preset("cornell-box", 1.0, seed=3)
+    s.commit(device=0)
+    w, h, spp = 44, 21, 3  # ragged: 6 x 3 tiles, the last column and row partly outside
+    rt = rtw.Raytracer(s, cam, bg, w, h, spp, seed=5)
+    full, st = rt.render()
+    knobs.setenv("RTW_BATCH", "100")
+    again, st2 = rt.render()
+    assert st2["rays"] == st["rays"]
+    assert np.array_equal(again.view(np.uint32), full.view(np.uint32))
+    nt = rtw.n_tiles(w, h)
+    stream = torch.cuda.current_stream().cuda_stream
+    for world in (1, 2, 5):
+        img = torch.zeros((h, w, 3), dtype=torch.float32, device="cuda:0")
+        rays = 0
+        for rank in range(world):
+            ids = torch.arange(rank, nt, world, dtype=torch.int32, device="cuda:0")
+            packed = torch.zeros((len(ids), 64, 3), dtype=torch.float32, device="cuda:0")
+            rays += rt.render_device(packed.data_ptr(), 0, ids.data_ptr(), len(ids), stream, want_stats=True)["rays"]
+            rtw.unpack_tiles_device(w, h, ids.data_ptr(), len(ids), packed.data_ptr(), img.data_ptr(), 0, stream)
+        torch.cuda.synchronize()
+        assert rays == st["rays"], (world, rays, st["rays"])
         assert np.array_equal(img.cpu().numpy().view(np.uint32), full.view(np.uint32)), world
 
 
