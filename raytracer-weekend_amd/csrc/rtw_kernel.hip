@@ -23,7 +23,10 @@
 // loops: regenerate -> trace_begin (the always-tested list) -> trace_run (resumable BVH4 walk with
 // postponed leaves; returns once quota16/16 of the lanes are done) -> shade.  A finished path writes
 // its radiance to an ordered sample buffer that reduce_kernel sums per pixel in sample order.
-// Variants (pick_kernel): feature-specialised instantiations; the LDS-node kernel for sphere worlds whose
+// Variants: path_kernel<COUNT, KernelCfg K> -- one plain aggregate (stack rows, spill, waves / SIMD, feature set,
+// workgroup size, LDS node table, half nodes, 16-bit stack) is the template argument, defines every property derived
+// from it, and travels with the kernel to the host (Variant), which sizes the launch from it.  pick_kernel names the
+// configurations: feature-specialised instantiations; the LDS-node kernel for sphere worlds whose
 // tree fits (the whole node table in LDS, sorted-push walk over 16-bit child codes; by default 1024-lane
 // workgroups, 2 per CU at 8 waves/SIMD, with the paths' T / depth / id in LDS rows: DESIGN.md §3); the
 // global-node kernels (256-lane workgroups, 32-bit LDS stack) for meshes, with half-precision nodes
@@ -1835,29 +1838,55 @@ __device__ __forceinline__ bool start_path(const StartArgs& a, uint64_t pid, Pat
   return true;
 }
 
-// BLK: workgroup size (256, or 512 for the LDS-node variants: one copy of the node table serves 8
-// waves).  NCAP: capacity of the LDS node table in node4s (0 = nodes read from global memory).
-template <bool COUNT, int STACK, bool SPILL, int OCC, uint32_t FEAT, int BLK = BLOCK, int NCAP = 0, bool HN = false,
-          bool S16 = false>
-__global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(OCC, 8))) void path_kernel(RenderArgs a) {
+// A path kernel's compile-time configuration: path_kernel's template argument, and what the host sizes its launch
+// from (Variant).  Everything derived from the fields is defined here, once.
+struct KernelCfg {
+  int stack;           // LDS stack rows per lane (the branch-free push's extra row not counted)
+  bool spill;          // a push bound beyond them goes to HBM (RenderArgs::spill)
+  int occ;             // waves per SIMD the register allocator must allow
+  uint32_t feat;       // Feature set (rtw_device.hpp), F_LIST for the BVH-less kernels
+  int blk = BLOCK;     // workgroup size (256; 448, 512 or 1024 for the LDS-node variants: one copy of the node
+                       // table serves the whole workgroup)
+  int ncap = 0;        // capacity of the LDS node table in node4s (0 = nodes read from global memory)
+  bool half = false;   // the walk reads the half-precision node table (DevNode4h)
+  bool s16 = false;    // the global-node walk keeps 16-bit stack entries (trace_run S16)
+  // the LDS-node kernel (sorted-push walk over the node table in LDS; no HBM spill path)
+  constexpr bool lds_nodes() const { return ncap > 0; }
+  // LST: the paths' T / depth / id in 10 more 16-bit rows after the stack (the S16 walk's column has stack + 1 rows)
+  constexpr int lst_rows() const { return ((ncap > 0 && blk == 1024) || s16) ? 10 : 0; }
+  constexpr int lst_row0() const { return stack + (s16 ? 1 : 0); }
+  constexpr bool lst() const { return lst_rows() > 0; }
+  constexpr bool shard() const { return ncap > 0; }  // SHARD: several path-id dispensers (path_kernel)
+  // SRING: path starts from the wave's ring of 64 (path_kernel; the rect list kernel only)
+  constexpr bool sring() const { return RTW_SRING && feat == (F_BOXES | F_LIST) && !lst(); }
+  // the S16 half-node mesh walk keeps the tree's top RTW_MESH_ROOT node4s in LDS (trace_run ROOT)
+  constexpr bool root_lds() const { return half && s16 && ncap == 0 && RTW_MESH_ROOT > 0; }
+  constexpr bool alignbit_draws() const { return !(feat & F_TRI); }                // AB: the one-alignbit draws
+  constexpr bool start_args_in_lds() const { return alignbit_draws() || s16; }     // SLDS (path_kernel)
+  constexpr uint32_t node_quads() const { return half ? 7u : 8u; }  // 16-B quads per node (DevNode4h / DevNode4)
+  constexpr bool codes16_stack() const { return ncap > 0 || s16; }  // the LDS stack holds 16-bit entries (stk16)
+  constexpr int far_lds_nodes() const { return half ? 0 : ncap; }   // trace_far reads f32 nodes: from LDS if there
+};
+
+template <bool COUNT, KernelCfg K>
+__global__ __launch_bounds__(K.blk) __attribute__((amdgpu_waves_per_eu(K.occ, 8))) void path_kernel(RenderArgs a) {
   // + 1: trace_run's branch-free push.  LDS-node variants use 16-bit entries, STACK rows (window included);
   // S16 (global nodes, 16-bit entries): STACK + 1 rows of 16 bits
-  __shared__ int32_t stk_all[(NCAP > 0 || S16) ? 1 : (STACK + 1) * BLK];
+  __shared__ int32_t stk_all[K.codes16_stack() ? 1 : (K.stack + 1) * K.blk];
   // LST: 10 more 16-bit rows after the stack hold the path state (below)
   // (the S16 mesh walk too: its 16-bit stack column has STACK + 1 rows, the state rows follow them)
-  constexpr int LST_ROWS = ((NCAP > 0 && BLK == 1024) || S16) ? 10 : 0;
-  constexpr int LST_ROW0 = STACK + (S16 ? 1 : 0);
-  __shared__ uint16_t stk16_all[NCAP > 0 ? (STACK + LST_ROWS) * BLK : (S16 ? (STACK + 1 + LST_ROWS) * BLK : 1)];
-  constexpr uint32_t NODE_Q = HN ? 7u : 8u;  // 16-B quads per node (DevNode4h / DevNode4)
+  __shared__ uint16_t stk16_all[K.ncap > 0 ? (K.stack + K.lst_rows()) * K.blk
+                                           : (K.s16 ? (K.stack + 1 + K.lst_rows()) * K.blk : 1)];
   // (the S16 half-node mesh walk: the root node only, trace_run ROOT)
-  constexpr bool ROOT_LDS = HN && S16 && NCAP == 0 && RTW_MESH_ROOT > 0;
-  __shared__ float4 nodes_lds[NCAP > 0 ? NCAP * NODE_Q : (ROOT_LDS ? RTW_MESH_ROOT * NODE_Q : 1)];
-  if constexpr (NCAP > 0) {  // the host launches this variant only when Flat::codes16 and n_nodes <= NCAP
-    const float4* g = HN ? reinterpret_cast<const float4*>(a.scene.hnodes) : reinterpret_cast<const float4*>(a.scene.nodes);
-    for (uint32_t k = threadIdx.x; k < a.scene.n_nodes * NODE_Q; k += BLK) nodes_lds[k] = g[k];
+  __shared__ float4 nodes_lds[K.ncap > 0 ? K.ncap * K.node_quads()
+                                         : (K.root_lds() ? RTW_MESH_ROOT * K.node_quads() : 1)];
+  if constexpr (K.ncap > 0) {  // the host launches this variant only when Flat::codes16 and n_nodes <= NCAP
+    const float4* g = K.half ? reinterpret_cast<const float4*>(a.scene.hnodes)
+                             : reinterpret_cast<const float4*>(a.scene.nodes);
+    for (uint32_t k = threadIdx.x; k < a.scene.n_nodes * K.node_quads(); k += K.blk) nodes_lds[k] = g[k];
   }
-  if constexpr (ROOT_LDS) {
-    const uint32_t nq = min(a.scene.n_nodes, (uint32_t)RTW_MESH_ROOT) * NODE_Q;
+  if constexpr (K.root_lds()) {
+    const uint32_t nq = min(a.scene.n_nodes, (uint32_t)RTW_MESH_ROOT) * K.node_quads();
     if (threadIdx.x < nq) nodes_lds[threadIdx.x] = reinterpret_cast<const float4*>(a.scene.hnodes)[threadIdx.x];
   }
   // start_path's operands from LDS in the sphere and list-mode variants (their SGPR spills, and every
@@ -1866,20 +1895,18 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(OCC, 8))) v
   // cow-1080p +6.7% (profiles/r05/experiments, m1).  The 5-wave mesh variants keep the kernel arguments (their
   // paths regenerate every ~2 segments: 5-7% slower with the LDS reads in round 3).  The one-alignbit draws (AB)
   // stay with the sphere and list-mode kernels (the triangle kernels' register allocation lost 1-2% with them).
-  constexpr bool AB = !(FEAT & F_TRI);
-  constexpr bool SLDS = AB || S16;
-  __shared__ StartArgs start_lds[SLDS ? 1 : 0 + 1];
+  __shared__ StartArgs start_lds[K.start_args_in_lds() ? 1 : 0 + 1];
   StartArgs sa_reg;
-  if constexpr (SLDS) {
+  if constexpr (K.start_args_in_lds()) {
     if (threadIdx.x == 0) fill_start_args(a, start_lds[0]);
   } else {
     fill_start_args(a, sa_reg);
   }
-  const StartArgs& SA = SLDS ? start_lds[0] : sa_reg;
+  const StartArgs& SA = K.start_args_in_lds() ? start_lds[0] : sa_reg;
   __syncthreads();
   uint16_t* stk16 = stk16_all + threadIdx.x;
   int32_t* stk = stk_all + threadIdx.x;
-  int32_t* spill = a.spill + (size_t)blockIdx.x * BLK + threadIdx.x;  // unused unless spill_depth > 0
+  int32_t* spill = a.spill + (size_t)blockIdx.x * K.blk + threadIdx.x;  // unused unless spill_depth > 0
   const uint32_t lane = threadIdx.x & 63u;
   // LST (1024-lane LDS-node workgroups, 2 per CU: half the node-table copies of 512-lane ones): a path's
   // throughput, remaining depth and id live in LDS, not VGPRs.  At 8 waves / SIMD (64 VGPRs) the compiler
@@ -1888,13 +1915,14 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(OCC, 8))) v
   // Each 32-bit value is two 16-bit rows of the lane's stack column (rows STACK.. STACK + 9: T.x, T.y, T.z,
   // depth, id), addressed from the stack pointer with constant offsets: separate per-lane LDS pointers were
   // loop-invariant VGPRs, which the compiler spilled in turn.
-  constexpr bool LST = LST_ROWS > 0;
+  // (a local copy: with K.lst() in the selects below, the rect list kernels' prologue came out in another order)
+  constexpr bool LST = K.lst();
   auto lst_st = [&](int k, uint32_t v) {
-    stk16[(LST_ROW0 + 2 * k) * BLK] = (uint16_t)v;
-    stk16[(LST_ROW0 + 2 * k + 1) * BLK] = (uint16_t)(v >> 16);
+    stk16[(K.lst_row0() + 2 * k) * K.blk] = (uint16_t)v;
+    stk16[(K.lst_row0() + 2 * k + 1) * K.blk] = (uint16_t)(v >> 16);
   };
   auto lst_ld = [&](int k) -> uint32_t {
-    return (uint32_t)stk16[(LST_ROW0 + 2 * k) * BLK] | ((uint32_t)stk16[(LST_ROW0 + 2 * k + 1) * BLK] << 16);
+    return (uint32_t)stk16[(K.lst_row0() + 2 * k) * K.blk] | ((uint32_t)stk16[(K.lst_row0() + 2 * k + 1) * K.blk] << 16);
   };
   const DevScene& S = a.scene;
   const V3 bg = ld3(a.bg);
@@ -1907,7 +1935,6 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(OCC, 8))) v
   // grid serialises its atomics: the small batches of small passes -- configs[0], an 8-GPU share's short end-of-pass
   // tail -- queued behind it (r06, share8: jumpy's 1/8 share +5%, configs[0] +11%).  The other kernels keep the one
   // word (their code with the dispenser loop ran 1.2-1.8% slower on full frames: cornell, monument).
-  constexpr bool SHARD = NCAP > 0;
   unsigned long long* const dispenser = a.queue;
   const uint32_t batch = a.batch, ndisp = batch < 1024u ? DISP : 1u;
   const uint64_t NB = (P + batch - 1u) / batch;  // batches in the pass
@@ -1915,13 +1942,13 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(OCC, 8))) v
   unsigned long long nrays = 0;
   // the wave's id pool [next, end) lives in LDS between regenerations: loop-carried 64-bit
   // uniforms otherwise end up as VGPR phis that the 6-wave sphere variant has to spill
-  __shared__ uint64_t pool_lds[BLK / 64][SHARD ? 5 : 3];
+  __shared__ uint64_t pool_lds[K.blk / 64][K.shard() ? 5 : 3];
   // S16 mesh walk: the wave index as a scalar, so the pool address is rebuilt from an SGPR (one v_mov) where it is
   // used instead of kept in a VGPR (the 7-wave walk spilled it to scratch and reloaded it at every regeneration;
   // the sphere and list-mode kernels measured 0.5-1.4% slower with it, profiles/r05/experiments s1)
-  uint64_t* const pool = pool_lds[S16 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6];
+  uint64_t* const pool = pool_lds[K.s16 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6];
   if (lane == 0) { pool[0] = 0; pool[1] = 0; }
-  if (SHARD && lane == 0) pool[SHARD ? 4 : 0] = 0;
+  if (K.shard() && lane == 0) pool[K.shard() ? 4 : 0] = 0;
   // the wave's next batch [b, e) of path ids (b = e = P: none left); lane 0 takes it, every lane reads it
   auto refill = [&](uint64_t& b, uint64_t& e) {  // (SHARD)
     if (lane == 0) {
@@ -1937,11 +1964,11 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(OCC, 8))) v
         }
       }
       pool[2] = bb;
-      pool[SHARD ? 3 : 0] = ee;
-      pool[SHARD ? 4 : 0] = k;
+      pool[K.shard() ? 3 : 0] = ee;
+      pool[K.shard() ? 4 : 0] = k;
     }
     b = rfl64(pool[2]);
-    e = rfl64(pool[SHARD ? 3 : 0]);
+    e = rfl64(pool[K.shard() ? 3 : 0]);
   };
   // SRING: the wave's ring of 64 path starts, made by all 64 lanes at once from 64 consecutive ids of its pool and
   // taken by the lanes that regenerate (start_path is a function of the id alone, so which lane makes a path's start
@@ -1949,12 +1976,11 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(OCC, 8))) v
   // Per lane slot: o, d, time, rng (2 words), pid (10 words, structure of arrays); rng = 0 marks an off-image id.
   // (the rect list kernel only: its LDS is free and its VGPRs hold the generation; the LDS-node and mesh kernels have
   // no LDS left for 2.5 KB per wave at their occupancy)
-  constexpr bool SRING = RTW_SRING && FEAT == (F_BOXES | F_LIST) && !LST;
-  __shared__ uint32_t ring_lds[SRING ? (BLK / 64) * 640 : 1];
-  __shared__ uint32_t ring_head_lds[SRING ? BLK / 64 : 1];
-  uint32_t* const ring = ring_lds + (SRING ? (threadIdx.x >> 6) * 640u : 0u);
-  uint32_t* const ring_head = ring_head_lds + (SRING ? threadIdx.x >> 6 : 0u);
-  if (SRING && lane == 0) ring_head[0] = 64u;
+  __shared__ uint32_t ring_lds[K.sring() ? (K.blk / 64) * 640 : 1];
+  __shared__ uint32_t ring_head_lds[K.sring() ? K.blk / 64 : 1];
+  uint32_t* const ring = ring_lds + (K.sring() ? (threadIdx.x >> 6) * 640u : 0u);
+  uint32_t* const ring_head = ring_head_lds + (K.sring() ? threadIdx.x >> 6 : 0u);
+  if (K.sring() && lane == 0) ring_head[0] = 64u;
   bool exhausted = false;                // wave-uniform
   bool has = false;
   TraceState ts;
@@ -1979,7 +2005,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(OCC, 8))) v
     phase(2);
     // ---- regeneration: compact new path ids into the idle lanes
     const uint64_t need = __ballot(!has);
-    if constexpr (SRING) {
+    if constexpr (K.sring()) {
       if (need != 0 && !exhausted && ((uint32_t)__popcll(need) >= a.regen_min || need == __ballot(1))) {
         const uint32_t n_need = (uint32_t)__popcll(need);
         const uint32_t rank =
@@ -2004,7 +2030,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(OCC, 8))) v
         if (n_need > have) {  // the ring is spent: 64 more starts from the pool (refilled by one atomic per batch)
           uint64_t pool_next = rfl64(pool[0]), pool_end = rfl64(pool[1]);
           if (pool_next >= pool_end) {
-            if constexpr (SHARD) {
+            if constexpr (K.shard()) {
               refill(pool_next, pool_end);
             } else {
               if (lane == 0) pool[2] = atomicAdd(dispenser, (unsigned long long)batch);
@@ -2018,7 +2044,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(OCC, 8))) v
           if (pool_next < pool_end) {
             const uint64_t id = pool_next + lane;
             PathState g;
-            const bool ok = start_path<SLDS, 0, 0, AB>(SA, id, g);
+            const bool ok = start_path<K.start_args_in_lds(), 0, 0, K.alignbit_draws()>(SA, id, g);
             ring[lane] = __float_as_uint(g.ray.o.x);
             ring[64 + lane] = __float_as_uint(g.ray.o.y);
             ring[2 * 64 + lane] = __float_as_uint(g.ray.o.z);
@@ -2053,7 +2079,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(OCC, 8))) v
       if (avail < n_need) {  // refill: one atomic per BATCH paths
         // lane 0 takes BATCH ids and hands them to the wave through LDS (a `b = 0` default
         // for the other lanes would be one more loop-carried VGPR pair)
-        if constexpr (SHARD) {
+        if constexpr (K.shard()) {
           uint64_t b, e;
           refill(b, e);
           if (b < e) {
@@ -2076,7 +2102,8 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(OCC, 8))) v
       const uint64_t t_sp = COUNT ? __builtin_amdgcn_s_memtime() : 0;
       if (!has) {
         const uint64_t id = rank < avail ? pool_next + rank : nb + (rank - avail);
-        if ((rank < avail || id < ne) && start_path<SLDS, LST ? BLK : 0, LST_ROW0, AB>(SA, id, st, stk16)) {
+        if ((rank < avail || id < ne) &&
+            start_path<K.start_args_in_lds(), LST ? K.blk : 0, K.lst_row0(), K.alignbit_draws()>(SA, id, st, stk16)) {
           has = true;
         }
       }
@@ -2103,15 +2130,15 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(OCC, 8))) v
     if (!has) continue;
     // ---- one segment: closest hit (resumable) + shading (lib.rs:97-117)
     if (!ts.on) {
-      trace_begin<COUNT, FEAT, STACK, BLK, (NCAP > 0 || S16), (HN ? 0 : NCAP)>(S, st.ray, ts, cnt, st.rng, stk16, stk,
-                                                                              a.err, nodes_lds);
+      trace_begin<COUNT, K.feat, K.stack, K.blk, K.codes16_stack(), K.far_lds_nodes()>(S, st.ray, ts, cnt, st.rng, stk16,
+                                                                                       stk, a.err, nodes_lds);
     }
-    if (!(FEAT & F_LIST)) {
+    if (!(K.feat & F_LIST)) {
       const uint32_t act = (uint32_t)__popcll(__ballot(1));
       const uint32_t quota = (act * a.quota16 + 15u) >> 4;
       const uint32_t leaf_thr = (act * a.leaf16 + 15u) >> 4;
-      trace_run<COUNT, STACK, SPILL, FEAT, BLK, NCAP, HN, S16>(S, st.ray, ts, stk, spill, a.spill_lanes, cnt, quota,
-                                                      leaf_thr, st.rng, a.err, ph + 4, nodes_lds, stk16);
+      trace_run<COUNT, K.stack, K.spill, K.feat, K.blk, K.ncap, K.half, K.s16>(S, st.ray, ts, stk, spill, a.spill_lanes, cnt,
+                                                                              quota, leaf_thr, st.rng, a.err, ph + 4, nodes_lds, stk16);
     } else {
       ts.node = -1;  // list mode: trace_begin tested every primitive
       ts.sp = 0;
@@ -2132,10 +2159,10 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(OCC, 8))) v
     V3 L = mk(0.f, 0.f, 0.f);
     // the throughput; the S16 mesh walk reads it from its LDS rows where it is used, after the hit record and the
     // material, so it is not held across them (the 7-wave walk had spilled T.z to scratch there; s1)
-    const V3 T0 = (LST && !S16) ? mk(__uint_as_float(lst_ld(0)), __uint_as_float(lst_ld(1)), __uint_as_float(lst_ld(2)))
+    const V3 T0 = (LST && !K.s16) ? mk(__uint_as_float(lst_ld(0)), __uint_as_float(lst_ld(1)), __uint_as_float(lst_ld(2)))
                                 : st.T;
     auto path_T = [&]() -> V3 {
-      return (LST && S16) ? mk(__uint_as_float(lst_ld(0)), __uint_as_float(lst_ld(1)), __uint_as_float(lst_ld(2))) : T0;
+      return (LST && K.s16) ? mk(__uint_as_float(lst_ld(0)), __uint_as_float(lst_ld(1)), __uint_as_float(lst_ld(2))) : T0;
     };
     if (b.prim < 0) {  // lib.rs:102-105
       L = mul(path_T(), bg);
@@ -2144,7 +2171,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(OCC, 8))) v
         // trace_run tripped its guard (a corrupt tree; the frame is invalid and reported): close the path queue
         // for every wave and empty this wave's id pool, so the grid drains after about one trip per wave
         // instead of one per 64 paths (a trip is 2^20 node-loop iterations)
-        if constexpr (SHARD) {
+        if constexpr (K.shard()) {
           for (uint32_t d = 0; d < DISP; ++d) atomicMax(dispenser + d * DISP_STRIDE, (unsigned long long)NB);
         } else {
           atomicMax(dispenser, (unsigned long long)P);
@@ -2167,9 +2194,9 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(OCC, 8))) v
       // a light of one solid colour (light_source.rs:17-24 with SolidColor) needs no hit record: its
       // emission is the colour and it never scatters (the cow's emitting mesh; mesh kernels only: the
       // extra branch measured 0.7% slower on cornell-box)
-      const bool solid_light = (FEAT & F_LIGHT) && (FEAT & F_TRI) && (sh.kind & 0xfffu) == (MT_LIGHT | (SM_SOLID << 8));
+      const bool solid_light = (K.feat & F_LIGHT) && (K.feat & F_TRI) && (sh.kind & 0xfffu) == (MT_LIGHT | (SM_SOLID << 8));
       Rec h;
-      if (!solid_light) h = hit_record<FEAT>(S, st.ray, b, sh.kind);
+      if (!solid_light) h = hit_record<K.feat>(S, st.ray, b, sh.kind);
       else h = Rec{mk(0.f, 0.f, 0.f), mk(0.f, 0.f, 0.f), 0.0f, 0.0f, true, 0u};
 #ifdef RTW_SHADE_DIAG  // COUNT-build diagnostic: shading sub-phases (hit record, unit + texture, scatter) in ph[7..9]
       phase(7);
@@ -2178,13 +2205,13 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(OCC, 8))) v
       // materials runs the rejection loop, unit() and the texture lookup once instead of once per
       // material branch.  Each material's draws and f32 operations are unchanged.
       const uint32_t mt = sh.kind & 0xffu, mode = (sh.kind >> 8) & 0xfu;
-      const bool light = (FEAT & F_LIGHT) && mt == MT_LIGHT;
-      const bool lam = (FEAT & F_LAMBERT) && mt == MT_LAMBERT;
-      const bool met = (FEAT & F_METAL) && mt == MT_METAL;
-      const bool iso = (FEAT & F_ISO) && mt == MT_ISOTROPIC;
+      const bool light = (K.feat & F_LIGHT) && mt == MT_LIGHT;
+      const bool lam = (K.feat & F_LAMBERT) && mt == MT_LAMBERT;
+      const bool met = (K.feat & F_METAL) && mt == MT_METAL;
+      const bool iso = (K.feat & F_ISO) && mt == MT_ISOTROPIC;
       V3 rs = mk(0.f, 0.f, 0.f);
       phase(2);
-      if (lam || met || iso) rs = rand_in_unit_sphere<AB>(st.rng);  // vec3.rs:101-108
+      if (lam || met || iso) rs = rand_in_unit_sphere<K.alignbit_draws()>(st.rng);  // vec3.rs:101-108
       phase(3);
       const V3 ud = unit(lam ? rs : st.ray.d);                  // Lambertian: unit(rs); else unit(d_in)
       V3 att = mk(1.f, 1.f, 1.f);                                 // Dielectric: attenuation (1,1,1)
@@ -2192,12 +2219,12 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(OCC, 8))) v
         att = ld3(sh.a);
       } else if (light || lam || iso) {
         if (mode == SM_SOLID) att = ld3(sh.a);  // SolidColor::value
-        else if ((FEAT & F_CHECKER) && mode == SM_CHECKER)
+        else if ((K.feat & F_CHECKER) && mode == SM_CHECKER)
           att = checker_odd(sh.param * h.p.x, sh.param * h.p.y, sh.param * h.p.z) ? ld3(sh.a)
                                                                                    : ld3(LST ? S.shade[b.prim].b : sh.b);
-        else if ((FEAT & F_IMAGE) && mode == SM_IMAGE)  // (the monument's texture: no record chain)
+        else if ((K.feat & F_IMAGE) && mode == SM_IMAGE)  // (the monument's texture: no record chain)
           att = image_texel(S, __float_as_uint(sh.a[0]), __float_as_uint(sh.a[1]), __float_as_uint(sh.a[2]), h.u, h.v);
-        else if (FEAT & F_TEXGEN) att = tex_value<FEAT>(S, S.mats[h.mat].tex, h.u, h.v, h.p);
+        else if (K.feat & F_TEXGEN) att = tex_value<K.feat>(S, S.mats[h.mat].tex, h.u, h.v, h.p);
       }
 #ifdef RTW_SHADE_DIAG
       phase(8);
@@ -2214,7 +2241,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(OCC, 8))) v
         } else if (met) {  // material.rs:78-95
           dir = add(reflect(ud, h.n), scale(rs, sh.param));
           done = !(dot(dir, h.n) > 0.0f);  // absorbed: emitted() is black
-        } else if (!iso && (FEAT & F_DIEL)) {  // Dielectric, material.rs:116-142
+        } else if (!iso && (K.feat & F_DIEL)) {  // Dielectric, material.rs:116-142
           // 1 / ir (material.rs:120) and Schlick's r0 (:108-112) for both ratios: the same f32
           // operations, evaluated once by the flattener (DevShade::a)
           const float ratio = h.front ? sh.a[0] : sh.param;
@@ -2382,71 +2409,98 @@ __global__ void sweep_kernel(int fn, uint32_t lo, uint32_t hi, unsigned long lon
 
 }  // namespace dev
 
-// Variants of the path kernel: feature set x the waves per SIMD the register allocator must allow.
-// Sphere-only scenes (jumpy-balls) get the specialised kernel; everything else the generic one.
-// Trees whose push bound exceeds the LDS stack get the SPILL variant.  Default: 5 waves/SIMD.
-// Tuning knobs: RTW_OCC=4 (33-row stack) or RTW_OCC=6 (specialised kernel; spills registers);
-// RTW_STACK_LDS=4 selects a generic kernel with a 4-entry LDS stack, so that the HBM spill path
-// runs on every scene (tests/test_gpu_parity.py).
 typedef void (*path_fn)(RenderArgs);
-static int env_int(const char* k, int dflt) {  // a tuning knob (read only with RTW_TUNING=1)
-  const char* e = strcmp(k, "RTW_VERBOSE") ? tuning_env(k) : getenv(k);  // RTW_VERBOSE only prints
-  return e ? atoi(e) : dflt;
-}
+using dev::KernelCfg;
 struct Variant {
   path_fn fn;
-  uint32_t stack;        // LDS stack rows of fn; a deeper push bound spills to HBM (RenderArgs::spill)
-  uint32_t block = 256;  // workgroup size fn is compiled for
-  bool k16 = false;      // LDS-node kernel (sorted-push walk)
-  bool sring = false;    // path starts from the wave's ring (path_kernel SRING)
+  KernelCfg cfg;  // what fn was compiled for: the launch (grid, stack / spill split, batch) is sized from it
 };
+template <bool C, KernelCfg K>
+static Variant make_variant() { return {dev::path_kernel<C, K>, K}; }  // the only way a Variant is made
+constexpr KernelCfg with_half(KernelCfg k) { k.half = true; return k; }    // ... reading the half-precision nodes
+constexpr KernelCfg with_spill(KernelCfg k) { k.spill = true; return k; }  // ... with the HBM stack spill
+
+// A tuning knob: unset, or its value.  Knobs holds every knob this file reads, filled once per
+// render / introspection call by read_knobs(): the selection and the launch parameters take them from there.
+struct Knob {
+  bool set = false;
+  int v = 0;
+  int get(int dflt) const { return set ? v : dflt; }
+};
+struct Knobs {
+  Knob stack_lds, half_nodes, generic, list_all, list_occ, occ, ldsn_waves, lds_nodes, ldsn_blk, mesh_s16;  // selection
+  Knob batch, quota16, leaf16, regen_min, pass_log2;                                                        // launch
+  bool verbose = false;
+};
+
+// The configurations the selection below names.  The 32-bit-stack walks over global nodes, per feature set F:
+template <uint32_t F> constexpr KernelCfg WALK4{.stack = dev::STACK_LDS, .spill = false, .occ = 4, .feat = F};
+template <uint32_t F> constexpr KernelCfg WALK5{.stack = dev::STACK_LDS5, .spill = false, .occ = 5, .feat = F};
+template <uint32_t F> constexpr KernelCfg DEEP5{.stack = dev::STACK_DEEP5, .spill = false, .occ = 5, .feat = F};
+constexpr KernelCfg SPHERES6{.stack = dev::STACK_LDS5, .spill = false, .occ = 6, .feat = F_SPHERES};
+// a 4-entry LDS stack, so that the HBM spill path runs on every scene (RTW_STACK_LDS=4)
+constexpr KernelCfg SPILL_TEST{.stack = 4, .spill = true, .occ = 4, .feat = F_ALL};
+// no BVH (list mode): variants without the walk
+constexpr KernelCfg LIST_ALL{.stack = 1, .spill = false, .occ = 5, .feat = F_ALL | F_LIST};
+constexpr KernelCfg LIST_BOXES8{.stack = 1, .spill = false, .occ = 8, .feat = F_BOXES | F_LIST};
+constexpr KernelCfg LIST_BOXES6{.stack = 1, .spill = false, .occ = 6, .feat = F_BOXES | F_LIST};
 // LDS-node variants: the node table lives in each workgroup's LDS.  512-lane workgroups at 6
 // waves/SIMD = 3 per CU: 24 rows of 16-bit stack entries x 512 x 2 B + 224 node4s x 128 B + the pool
 // words = 53,440 B per workgroup, 160,320 B per CU (<= 160 KiB): sphere worlds of up to ~850 spheres.
-constexpr int LDSN_STACK = 24, LDSN_CAP = 224, LDSN_BLK = 512;
 // (The spheres' 32-B test records in LDS too -- 18 stack rows, 512 x 32 B -- and the winner's hit record
 // from them measured equal within 0.2%: profiles/r02/experiments n6, h2.)
+constexpr KernelCfg LDSN_224{.stack = 24, .spill = false, .occ = 6, .feat = F_SPHERES, .blk = 512, .ncap = 224};
+// 8 waves per SIMD when the tree fits a smaller table: 512-lane workgroups x 4 per CU, 144 node4s and 16
+// stack rows in 36 KB of LDS, 64 VGPRs (the compiler spills 32 B per lane to scratch, outside the node
+// loop).  The latency-bound kernel gains from the extra waves: jumpy-1080p 26.34k -> 27.02k Mrays/s
+// (profiles/r03/experiments, w1); 7 waves (448-lane workgroups, 160 node4s, 18 rows, 72 VGPRs) measured
+// slower (25.18k), as did both with half-precision nodes.  Knob RTW_LDSN_WAVES (6, 7, 8).
+constexpr KernelCfg LDSN_512{.stack = 16, .spill = false, .occ = 8, .feat = F_SPHERES, .blk = 512, .ncap = 144};
+constexpr KernelCfg LDSN_448{.stack = 18, .spill = false, .occ = 7, .feat = F_SPHERES, .blk = 448, .ncap = 160};
+// 1024-lane workgroups x 2 per CU (knob RTW_LDSN_BLK, 512 = the 4 x 512 form): one node table per 16
+// waves, and the LDS this frees holds the paths' T / depth / id (path_kernel LST) that the 64-VGPR
+// budget otherwise spills to scratch.  LDS per workgroup: 18 KB nodes + 32 KB stack + 20 KB state.
+constexpr KernelCfg LDSN_1024{.stack = 16, .spill = false, .occ = 8, .feat = F_SPHERES, .blk = 1024, .ncap = 144};
+// The mesh walk with 16-bit stack entries (the nodes' codes: half the LDS of the 32-bit stack, whose 31 KB per
+// workgroup allow 5 per CU) and the paths' T / depth / id in LDS state rows, at 6 or 7 waves / SIMD (knob
+// RTW_MESH_S16; 0 = the 32-bit stack at 5).  Measured (r04n, r04p): monument-4k +3.0% at 6 waves (80 VGPRs), +2.2%
+// more with the state rows (scratch 40 -> 32 B), 7 waves slower; cow-1080p -4.1% / -0.7% with the rows.  With the
+// start_path operands in LDS (round 5, m1) the SGPR overflow is gone and 7 waves (72 VGPRs) win: monument
+// +2.3%, cow +0.8% over 6 (profiles/r05/experiments, m2), so every tree with half nodes takes the 7-wave walk.
+template <uint32_t F>
+constexpr KernelCfg S16_7{.stack = dev::STACK_DEEP5, .spill = false, .occ = 7, .feat = F, .s16 = true};
+template <uint32_t F>
+constexpr KernelCfg S16_6{.stack = dev::STACK_DEEP5, .spill = false, .occ = 6, .feat = F, .s16 = true};
+
 template <bool C, uint32_t F>
-static Variant pick5(uint32_t need, bool half = false, bool codes16 = false) {
+static Variant pick5(const Knobs& kn, uint32_t need, bool half = false, bool codes16 = false) {
   using namespace dev;
   if constexpr (F == F_MESHES) {
-    // 16-bit stack entries (the nodes' codes: half the LDS of the 32-bit stack, whose 31 KB per workgroup allow
-    // 5 per CU) and the paths' T / depth / id in LDS state rows, at 6 or 7 waves / SIMD (knob RTW_MESH_S16; 0 =
-    // the 32-bit stack at 5).  Measured (r04n, r04p): monument-4k +3.0% at 6 waves (80 VGPRs), +2.2% more with
-    // the state rows (scratch 40 -> 32 B), 7 waves slower; cow-1080p -4.1% / -0.7% with the rows.  With the
-    // start_path operands in LDS (round 5, m1) the SGPR overflow is gone and 7 waves (72 VGPRs) win: monument
-    // +2.3%, cow +0.8% over 6 (profiles/r05/experiments, m2), so every tree with half nodes takes the 7-wave walk.
-    int s16 = env_int("RTW_MESH_S16", half ? 7 : 0);
+    int s16 = kn.mesh_s16.get(half ? 7 : 0);
     if (s16 != 0 && s16 != 6 && s16 != 7) {  //  no silent fallback for a value no variant has
       fprintf(stderr, "rtw: RTW_MESH_S16=%d ignored (0, 6 or 7)\n", s16);
       s16 = half ? 7 : 0;
     }
     if (codes16 && s16 != 0 && need <= (uint32_t)STACK_DEEP5) {
-      const uint32_t st = (uint32_t)STACK_DEEP5;
-      if (s16 == 7)
-        return half ? Variant{path_kernel<C, STACK_DEEP5, false, 7, F, BLOCK, 0, true, true>, st}
-                    : Variant{path_kernel<C, STACK_DEEP5, false, 7, F, BLOCK, 0, false, true>, st};
-      return half ? Variant{path_kernel<C, STACK_DEEP5, false, 6, F, BLOCK, 0, true, true>, st}
-                  : Variant{path_kernel<C, STACK_DEEP5, false, 6, F, BLOCK, 0, false, true>, st};
+      if (s16 == 7) return half ? make_variant<C, with_half(S16_7<F>)>() : make_variant<C, S16_7<F>>();
+      return half ? make_variant<C, with_half(S16_6<F>)>() : make_variant<C, S16_6<F>>();
     }
   }
   if constexpr (F == F_MESHES) {  // the half-precision node table (DevNode4h) where it was built
-    if (half && need <= (uint32_t)STACK_LDS5)
-      return {path_kernel<C, STACK_LDS5, false, 5, F, BLOCK, 0, true>, (uint32_t)STACK_LDS5};
-    if (half && need <= (uint32_t)STACK_DEEP5)
-      return {path_kernel<C, STACK_DEEP5, false, 5, F, BLOCK, 0, true>, (uint32_t)STACK_DEEP5};
+    if (half && need <= (uint32_t)STACK_LDS5) return make_variant<C, with_half(WALK5<F>)>();
+    if (half && need <= (uint32_t)STACK_DEEP5) return make_variant<C, with_half(DEEP5<F>)>();
   }
-  if (need <= (uint32_t)STACK_LDS5) return {path_kernel<C, STACK_LDS5, false, 5, F>, (uint32_t)STACK_LDS5};
+  if (need <= (uint32_t)STACK_LDS5) return make_variant<C, WALK5<F>>();
   if constexpr (F == F_MESHES || F == F_ALL) {
-    if (need <= (uint32_t)STACK_DEEP5) return {path_kernel<C, STACK_DEEP5, false, 5, F>, (uint32_t)STACK_DEEP5};
-    return {path_kernel<C, STACK_DEEP5, true, 5, F>, (uint32_t)STACK_DEEP5};
+    if (need <= (uint32_t)STACK_DEEP5) return make_variant<C, DEEP5<F>>();
+    return make_variant<C, with_spill(DEEP5<F>)>();
   }
-  return {path_kernel<C, STACK_LDS5, true, 5, F>, (uint32_t)STACK_LDS5};
+  return make_variant<C, with_spill(WALK5<F>)>();
 }
 // The mesh variants (F_MESHES) are compiled in their own translation unit, rtw_kernel_mesh.hip, with the
 // iterative-ILP machine scheduler instead of max-ILP (Makefile KFLAGS_MESH): cow +0.6%, monument +1.2%, where the
 // sphere and list-mode kernels lose 0.7-0.8% with it (profiles/r04/experiments k1)
-Variant pick_mesh(bool count, uint32_t need, bool half, bool codes16);
+Variant pick_mesh(bool count, const Knobs& kn, uint32_t need, bool half, bool codes16);
 
 #ifndef RTW_MESH_TU
 
@@ -2459,6 +2513,13 @@ static int hip_fail(hipError_t e, const char* what) {
     hipError_t e_ = (x);                         \
     if (e_ != hipSuccess) return hip_fail(e_, what); \
   } while (0)
+
+// restores the caller's current device on every return path
+struct DeviceGuard {
+  int prev = 0;
+  DeviceGuard() { hipGetDevice(&prev); }
+  ~DeviceGuard() { hipSetDevice(prev); }
+};
 
 template <class T>
 static size_t put(std::vector<uint8_t>& blob, const std::vector<T>& v) {
@@ -2487,14 +2548,13 @@ int upload(Scene& s, int device) {
   size_t o_shade = put(blob, f.shade), o_hnodes = put(blob, f.nodes4h), o_groups = put(blob, f.lgroups);
   blob.resize((blob.size() + 255) & ~(size_t)255);
   int d0 = device >= 0 ? device : 0, d1 = device >= 0 ? device + 1 : nlog;
-  int prev = 0;
-  hipGetDevice(&prev);
-  for (int d = d0; d < d1; ++d) {
+  DeviceGuard g;
+  // one device's copy, built in place in s.dev: release() frees whatever a failed step leaves behind
+  auto fill = [&](DeviceCopy& c, int d) -> int {
     const int phys = s.alias_n > 0 ? 0 : d;
-    HIPCHK(hipSetDevice(phys), "hipSetDevice");
-    DeviceCopy c;
     c.device = d;
     c.phys = phys;
+    HIPCHK(hipSetDevice(phys), "hipSetDevice");
     c.bytes = blob.size();
     HIPCHK(hipMalloc(&c.block, c.bytes), "hipMalloc(scene)");
     HIPCHK(hipMemcpy(c.block, blob.data(), c.bytes, hipMemcpyHostToDevice), "hipMemcpy(scene)");
@@ -2528,9 +2588,15 @@ int upload(Scene& s, int device) {
     c.scene.rect_fast = f.rect_fast;
     memcpy(c.scene.uni_off, f.uni_off, sizeof f.uni_off);
     c.scene.far_check = f.far_check;
-    s.dev.push_back(c);
+    return RTW_OK;
+  };
+  for (int d = d0; d < d1; ++d) {
+    s.dev.emplace_back();
+    if (int e = fill(s.dev.back(), d)) {
+      release(s);
+      return e;
+    }
   }
-  hipSetDevice(prev);
   return RTW_OK;
 }
 
@@ -2546,9 +2612,7 @@ void release(Scene& s) {
     if (c.block) hipFree(c.block);
     if (c.counters) hipFree(c.counters);
     if (c.err_host) hipHostFree(c.err_host);
-    if (c.sbuf) hipFree(c.sbuf);
-    if (c.spill) hipFree(c.spill);
-    for (DevBuf* b : {&c.image, &c.tiles, &c.packed, &c.gathered, &c.gather_ids}) free_buf(*b);
+    for (DevBuf* b : {&c.sbuf, &c.spill, &c.image, &c.tiles, &c.packed, &c.gathered, &c.gather_ids}) free_buf(*b);
     for (void* e : c.ev)
       if (e) hipEventDestroy(static_cast<hipEvent_t>(e));
     for (void* e : c.gev)
@@ -2591,17 +2655,48 @@ static int copy_events(DeviceCopy& c, hipEvent_t& e0, hipEvent_t& e1) {
 // Paths per pass (ordered sample buffer = 12 B per path): 2^32 = 51.5 GB of the 288 GB HBM.  A frame
 // with more paths (monument 4K x 1024 spp: 8.5 G, 2 passes) runs in several passes, each one persistent
 // launch + its in-order reduction.  Tuning knob RTW_PASS_LOG2 (24..33).
-static uint64_t max_pass_paths() {
-  const char* e = tuning_env("RTW_PASS_LOG2");
-  const int l = e ? std::min(32, std::max(24, atoi(e))) : 32;  // PathState::pid is 32-bit
-  return 1ull << l;
+static uint64_t max_pass_paths(const Knobs& kn) {
+  return 1ull << std::min(32, std::max(24, kn.pass_log2.get(32)));  // PathState::pid is 32-bit
 }
 
+// Every tuning knob of this file, read here and nowhere else (RTW_VERBOSE only prints: it needs no RTW_TUNING gate)
+static Knobs read_knobs() {
+  auto knob = [](const char* name) {
+    const char* e = tuning_env(name);
+    return e ? Knob{true, atoi(e)} : Knob{};
+  };
+  Knobs k;
+  k.stack_lds = knob("RTW_STACK_LDS");
+  k.half_nodes = knob("RTW_HALF_NODES");
+  k.generic = knob("RTW_GENERIC");
+  k.list_all = knob("RTW_LIST_ALL");
+  k.list_occ = knob("RTW_LIST_OCC");
+  k.occ = knob("RTW_OCC");
+  k.ldsn_waves = knob("RTW_LDSN_WAVES");
+  k.lds_nodes = knob("RTW_LDS_NODES");
+  k.ldsn_blk = knob("RTW_LDSN_BLK");
+  k.mesh_s16 = knob("RTW_MESH_S16");
+  k.batch = knob("RTW_BATCH");
+  k.quota16 = knob("RTW_QUOTA16");
+  k.leaf16 = knob("RTW_LEAF16");
+  k.regen_min = knob("RTW_REGEN_MIN");
+  k.pass_log2 = knob("RTW_PASS_LOG2");
+  const char* v = getenv("RTW_VERBOSE");
+  k.verbose = v && atoi(v);
+  return k;
+}
+
+// Variants of the path kernel: feature set x the waves per SIMD the register allocator must allow.
+// Sphere-only scenes (jumpy-balls) get the specialised kernel; everything else the generic one.
+// Trees whose push bound exceeds the LDS stack get the SPILL variant.  Default: 5 waves/SIMD.
+// Tuning knobs: RTW_OCC=4 (33-row stack) or RTW_OCC=6 (specialised kernel; spills registers);
+// RTW_STACK_LDS=4 selects a generic kernel with a 4-entry LDS stack, so that the HBM spill path
+// runs on every scene (tests/test_gpu_parity.py).
 template <bool C>
-static Variant pick_kernel(uint32_t feat, uint32_t need, bool list, uint32_t n_nodes, uint32_t need4,
+static Variant pick_kernel(const Knobs& kn, uint32_t feat, uint32_t need, bool list, uint32_t n_nodes, uint32_t need4,
                            bool codes16, bool has_half, bool far) {
   using namespace dev;
-  if (env_int("RTW_STACK_LDS", 0) == 4) return {path_kernel<C, 4, true, 4, F_ALL>, 4u};  // spill-path test
+  if (kn.stack_lds.get(0) == 4) return make_variant<C, SPILL_TEST>();  // spill-path test
   const bool sph = (feat & ~F_SPHERES) == 0;
   // Half-precision nodes (DevNode4h, built when the 16-bit codes fit) trade vector-memory traffic (4 loads /
   // 64 B per visit instead of 7 / 112 B) for VALU issue (v_fma_mix_f32 issues ~1.3x slower than v_fma_f32,
@@ -2610,97 +2705,93 @@ static Variant pick_kernel(uint32_t feat, uint32_t need, bool list, uint32_t n_n
   // mesh kernel.  With round 4's 6-wave mesh walk (16-bit stack, LDS state rows; pick5) the cow gains too (r04q:
   // +1.8%), so every mesh tree with a half table uses it by default; the LDS-node sphere kernels keep f32 nodes.
   // Knob RTW_HALF_NODES 1 = wherever built (LDS-node kernels too), 0 = never.
-  const int half_knob = env_int("RTW_HALF_NODES", -1);
+  const int half_knob = kn.half_nodes.get(-1);
   // (no half-precision table when a bound is beyond f16's range: rtw_flatten.cpp half_node)
   const bool half = has_half && half_knob != 0;
   const bool half_lds = has_half && half_knob > 0;
   if (list) {
     // RTW_GENERIC on a list world: the all-features LIST kernel, whose fold is the reference's (NaN candidates, list
     // order); the BVH kernels' fold treats a NaN candidate as a miss
-    if (env_int("RTW_GENERIC", 0)) return {path_kernel<C, 1, false, 5, F_ALL | F_LIST>, 1u};
-    // no BVH (list mode): variants without the walk.  The rect/instance one needs 56 VGPRs and
-    // runs at 8 waves/SIMD (cornell-box on MI355X: 26.7k Mrays/s at 5-6 waves, 28.9k at 7, 29.5k
-    // at 8; knob RTW_LIST_OCC); the all-features one spills below 96 VGPRs, so it stays at 5.
-    if ((feat & ~F_BOXES) == 0 && !env_int("RTW_LIST_ALL", 0)) {  // knob: the all-features list kernel instead
-      if (env_int("RTW_LIST_OCC", 8) == 6) return {path_kernel<C, 1, false, 6, F_BOXES | F_LIST>, 1u, 256u, false, RTW_SRING != 0};
-      return {path_kernel<C, 1, false, 8, F_BOXES | F_LIST>, 1u, 256u, false, RTW_SRING != 0};
+    if (kn.generic.get(0)) return make_variant<C, LIST_ALL>();
+    // The rect/instance list kernel needs 56 VGPRs and runs at 8 waves/SIMD (cornell-box on MI355X: 26.7k Mrays/s
+    // at 5-6 waves, 28.9k at 7, 29.5k at 8; knob RTW_LIST_OCC); the all-features one spills below 96 VGPRs, so
+    // it stays at 5.
+    if ((feat & ~F_BOXES) == 0 && !kn.list_all.get(0)) {  // knob: the all-features list kernel instead
+      if (kn.list_occ.get(8) == 6) return make_variant<C, LIST_BOXES6>();
+      return make_variant<C, LIST_BOXES8>();
     }
-    return {path_kernel<C, 1, false, 5, F_ALL | F_LIST>, 1u};
+    return make_variant<C, LIST_ALL>();
   }
   // sphere worlds default to 6 waves/SIMD (24 B/lane of register spill, +1.6% on jumpy-balls over
   // 5 waves once the kernel-uniform values left the VGPRs); the other variants to 5
-  switch (env_int("RTW_OCC", sph ? 6 : 5)) {
+  switch (kn.occ.get(sph ? 6 : 5)) {
     case 4: {
       const bool sp = need > (uint32_t)STACK_LDS;
-      const uint32_t st = (uint32_t)STACK_LDS;
-      if (sph) return {sp ? path_kernel<C, STACK_LDS, true, 4, F_SPHERES> : path_kernel<C, STACK_LDS, false, 4, F_SPHERES>, st};
-      return {sp ? path_kernel<C, STACK_LDS, true, 4, F_ALL> : path_kernel<C, STACK_LDS, false, 4, F_ALL>, st};
+      if (sph) return sp ? make_variant<C, with_spill(WALK4<F_SPHERES>)>() : make_variant<C, WALK4<F_SPHERES>>();
+      return sp ? make_variant<C, with_spill(WALK4<F_ALL>)>() : make_variant<C, WALK4<F_ALL>>();
     }
     case 6: {
-      // 8 waves per SIMD when the tree fits a smaller table: 512-lane workgroups x 4 per CU, 144 node4s and 16
-      // stack rows in 36 KB of LDS, 64 VGPRs (the compiler spills 32 B per lane to scratch, outside the node
-      // loop).  The latency-bound kernel gains from the extra waves: jumpy-1080p 26.34k -> 27.02k Mrays/s
-      // (profiles/r03/experiments, w1); 7 waves (448-lane workgroups, 160 node4s, 18 rows, 72 VGPRs) measured
-      // slower (25.18k), as did both with half-precision nodes.  Knob RTW_LDSN_WAVES (6, 7, 8).
-      const int ldsn_waves = env_int("RTW_LDSN_WAVES", 8);
-      if (sph && codes16 && env_int("RTW_LDS_NODES", 1) && ldsn_waves == 7 && need4 <= 18u && n_nodes <= 160u)
-        return half_lds ? Variant{path_kernel<C, 18, false, 7, F_SPHERES, 448, 160, true>, 18u, 448u, true}
-                        : Variant{path_kernel<C, 18, false, 7, F_SPHERES, 448, 160>, 18u, 448u, true};
-      // 1024-lane workgroups x 2 per CU (knob RTW_LDSN_BLK, 512 = the 4 x 512 form): one node table per 16
-      // waves, and the LDS this frees holds the paths' T / depth / id (path_kernel LST) that the 64-VGPR
-      // budget otherwise spills to scratch.  LDS per workgroup: 18 KB nodes + 32 KB stack + 20 KB state.
-      if (sph && codes16 && env_int("RTW_LDS_NODES", 1) && ldsn_waves == 8 && need4 <= 16u && n_nodes <= 144u &&
-          !half_lds && env_int("RTW_LDSN_BLK", 1024) == 1024)
-        return Variant{path_kernel<C, 16, false, 8, F_SPHERES, 1024, 144>, 16u, 1024u, true};
-      if (sph && codes16 && env_int("RTW_LDS_NODES", 1) && ldsn_waves == 8 && need4 <= 16u && n_nodes <= 144u)
-        return half_lds ? Variant{path_kernel<C, 16, false, 8, F_SPHERES, 512, 144, true>, 16u, 512u, true}
-                        : Variant{path_kernel<C, 16, false, 8, F_SPHERES, 512, 144>, 16u, 512u, true};
-      if (sph && codes16 && need4 <= (uint32_t)LDSN_STACK && n_nodes <= (uint32_t)LDSN_CAP &&
-          env_int("RTW_LDS_NODES", 1)) {
-        if (half_lds)
-          return {path_kernel<C, LDSN_STACK, false, 6, F_SPHERES, LDSN_BLK, LDSN_CAP, true>, (uint32_t)LDSN_STACK,
-                  (uint32_t)LDSN_BLK, true};
-        return {path_kernel<C, LDSN_STACK, false, 6, F_SPHERES, LDSN_BLK, LDSN_CAP>, (uint32_t)LDSN_STACK,
-                (uint32_t)LDSN_BLK, true};
-      }
-      if (sph && need <= (uint32_t)STACK_LDS5) return {path_kernel<C, STACK_LDS5, false, 6, F_SPHERES>, (uint32_t)STACK_LDS5};
+      // the LDS-node kernels (see their configurations): a sphere world whose sorted-push stack bound and node
+      // table fit the variant's rows and capacity
+      const int ldsn_waves = kn.ldsn_waves.get(8);
+      const bool ldsn = sph && codes16 && kn.lds_nodes.get(1);
+      auto fits = [&](const KernelCfg& k) { return need4 <= (uint32_t)k.stack && n_nodes <= (uint32_t)k.ncap; };
+      if (ldsn && ldsn_waves == 7 && fits(LDSN_448))
+        return half_lds ? make_variant<C, with_half(LDSN_448)>() : make_variant<C, LDSN_448>();
+      if (ldsn && ldsn_waves == 8 && fits(LDSN_1024) && !half_lds && kn.ldsn_blk.get(1024) == 1024)
+        return make_variant<C, LDSN_1024>();
+      if (ldsn && ldsn_waves == 8 && fits(LDSN_512))
+        return half_lds ? make_variant<C, with_half(LDSN_512)>() : make_variant<C, LDSN_512>();
+      if (ldsn && fits(LDSN_224))
+        return half_lds ? make_variant<C, with_half(LDSN_224)>() : make_variant<C, LDSN_224>();
+      if (sph && need <= (uint32_t)STACK_LDS5) return make_variant<C, SPHERES6>();
     }
       [[fallthrough]];
     default:
-      if (env_int("RTW_GENERIC", 0)) return pick5<C, F_ALL>(need);  // parity of the generic kernel
-      if (sph) return pick5<C, F_SPHERES>(need);
-      if ((feat & ~F_BOXES) == 0) return pick5<C, F_BOXES>(need);
-      if ((feat & ~F_SMOKE) == 0) return pick5<C, F_SMOKE>(need);
+      if (kn.generic.get(0)) return pick5<C, F_ALL>(kn, need);  // parity of the generic kernel
+      if (sph) return pick5<C, F_SPHERES>(kn, need);
+      if ((feat & ~F_BOXES) == 0) return pick5<C, F_BOXES>(kn, need);
+      if ((feat & ~F_SMOKE) == 0) return pick5<C, F_SMOKE>(kn, need);
       if ((feat & ~F_MESHES) == 0) {
         // a partial LDS node cache (the top 128 / 376 / 760 node4s, the rest from global memory, sorted-push
         // walk) measured slower on cow / monument (profiles/r02/experiments, n7): the full-table kernels
         // are for trees that fit
-        if (far) return pick5<C, F_ALL>(need);  // spheres in a mesh world's BVH: the mesh kernels have no far path
-        return pick_mesh(C, need, half, codes16);
+        if (far) return pick5<C, F_ALL>(kn, need);  // spheres in a mesh world's BVH: the mesh kernels have no far path
+        return pick_mesh(C, kn, need, half, codes16);
       }
-      return pick5<C, F_ALL>(need);
+      return pick5<C, F_ALL>(kn, need);
   }
 }
-static Variant path_kernel_variant(bool count, const Flat& f) {
+static Variant path_kernel_variant(bool count, const Flat& f, const Knobs& kn) {
   const uint32_t feat = f.features, need = f.stack_need, need4 = f.stack_need4, nn = (uint32_t)f.nodes4.size();
   const bool list = f.nodes4.empty();
   const bool hh = f.codes16 && !f.nodes4h.empty();
-  return count ? pick_kernel<true>(feat, need, list, nn, need4, f.codes16, hh, f.far_check != 0)
-               : pick_kernel<false>(feat, need, list, nn, need4, f.codes16, hh, f.far_check != 0);
+  return count ? pick_kernel<true>(kn, feat, need, list, nn, need4, f.codes16, hh, f.far_check != 0)
+               : pick_kernel<false>(kn, feat, need, list, nn, need4, f.codes16, hh, f.far_check != 0);
 }
 
-static int resident_grid(DeviceCopy& c, path_fn fn, uint32_t block, bool count) {
+// rtw_scene_info 16-23: the configuration of the path kernel the current environment selects for the committed
+// scene.  Host only: no device is touched.
+int64_t selected_kernel_info(const Scene& s, int field) {
+  const KernelCfg k = path_kernel_variant(false, s.flat, read_knobs()).cfg;
+  const int64_t v[8] = {k.stack, k.spill, k.occ, k.feat, k.blk, k.ncap, k.half, k.s16};
+  return field >= 0 && field < 8 ? v[field] : -1;
+}
+
+static int resident_grid(DeviceCopy& c, const Variant& var, bool count, bool verbose) {
+  const path_fn fn = var.fn;
+  const int block = var.cfg.blk;
   int& g = c.grid[count ? 1 : 0];
   void*& gf = c.grid_fn[count ? 1 : 0];
   if (g > 0 && gf == (void*)fn) return g;
   gf = (void*)fn;
   int per_cu = 0, cus = 0;
-  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, (int)block, 0);
+  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, block, 0);
   if (e != hipSuccess || per_cu < 1) per_cu = 1;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.phys) != hipSuccess || cus < 1) cus = 256;
   g = per_cu * cus;
-  if (env_int("RTW_VERBOSE", 0))
-    fprintf(stderr, "rtw: path kernel %p: block %u, %d resident blocks per CU x %d CUs\n", (void*)fn, block, per_cu, cus);
+  if (verbose)
+    fprintf(stderr, "rtw: path kernel %p: block %d, %d resident blocks per CU x %d CUs\n", (void*)fn, block, per_cu, cus);
   return g;
 }
 
@@ -2775,13 +2866,9 @@ int enqueue_render(Scene& sc, DeviceCopy& c, const rtw_camera* cam, const float 
   a.tile_stride = ts.stride;
   a.packed_out = (d_tiles || ts.packed) ? 1u : 0u;
   a.err = c.err_host;
-  // whole wave-loads of ids only (batch_ids): the start ring makes 64 path starts from 64 consecutive ids of a batch
-  a.batch = batch_ids(env_int("RTW_BATCH", (int)dev::BATCH));
-  a.quota16 = 12;  // see trace_run (measured best of 4..16 on jumpy-balls); tuning knob RTW_QUOTA16 (1..16)
-  if (const char* q = tuning_env("RTW_QUOTA16")) a.quota16 = (uint32_t)std::min(16, std::max(1, atoi(q)));
-  // test postponed leaves once leaf16/16 of the wave's lanes hold one and cannot descend (trace_run);
-  // knob RTW_LEAF16 (1..16)
-  a.leaf16 = (uint32_t)std::min(16, std::max(1, env_int("RTW_LEAF16", 3)));  // LDS-node variants: 5, below
+  const Knobs kn = read_knobs();
+  // see trace_run (measured best of 4..16 on jumpy-balls); tuning knob RTW_QUOTA16 (1..16)
+  a.quota16 = (uint32_t)std::min(16, std::max(1, kn.quota16.get(12)));
   // the host mirror of dev::splitmix64 (seed pre-hash shared by every pixel)
   uint64_t z = seed + 0x9E3779B97F4A7C15ull;
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -2797,28 +2884,24 @@ int enqueue_render(Scene& sc, DeviceCopy& c, const rtw_camera* cam, const float 
     HIPCHK(hipMemsetAsync(d_out, 0, n * sizeof(float), stream), "hipMemsetAsync(out)");
   } else if (n_slots) {
     const uint64_t per_slot = 64ull * spp;
-    const uint32_t slots_per_pass = (uint32_t)std::max<uint64_t>(1, max_pass_paths() / per_slot);
+    const uint32_t slots_per_pass = (uint32_t)std::max<uint64_t>(1, max_pass_paths(kn) / per_slot);
     const uint64_t need = std::min<uint64_t>(n_slots, slots_per_pass) * per_slot;
-    if (need > c.sbuf_paths) {  // grow the ordered sample buffer (first render only)
-      if (c.sbuf) HIPCHK(hipFree(c.sbuf), "hipFree(sample buffer)");
-      c.sbuf = nullptr;
-      c.sbuf_paths = 0;
-      HIPCHK(hipMalloc((void**)&c.sbuf, need * 3 * sizeof(float)), "hipMalloc(sample buffer)");
-      c.sbuf_paths = need;
-    }
-    a.sbuf = c.sbuf;
+    if (int e = grow(c.sbuf, need * 3 * sizeof(float))) return e;  // the ordered sample buffer (first render only)
+    a.sbuf = static_cast<float*>(c.sbuf.p);
     const bool count = flags & RTW_FLAG_COUNT_TRAVERSAL;
-    const Variant var = path_kernel_variant(count, sc.flat);
-    const path_fn fn = var.fn;
-    // the sorted-push walk of the LDS-node kernels parks fewer leaves early: 5/16 measured best on
-    // jumpy-balls (+0.5% over 3; profiles/r02/experiments, n5)
-    if (var.k16 && sc.flat.features == (sc.flat.features & F_SPHERES))
-      a.leaf16 = (uint32_t)std::min(16, std::max(1, env_int("RTW_LEAF16", 5)));
-    // the 1024-lane LDS-node kernel and the BVH-less list kernels: 1024 ids per atomic (a shorter end-of-frame
+    const Variant var = path_kernel_variant(count, sc.flat, kn);
+    const KernelCfg& k = var.cfg;
+    // test postponed leaves once leaf16/16 of the wave's lanes hold one and cannot descend (trace_run); knob
+    // RTW_LEAF16 (1..16).  The sorted-push walk of the LDS-node kernels parks fewer leaves early: 5/16 measured best
+    // on jumpy-balls (+0.5% over 3; profiles/r02/experiments, n5)
+    const bool ldsn_spheres = k.lds_nodes() && sc.flat.features == (sc.flat.features & F_SPHERES);
+    a.leaf16 = (uint32_t)std::min(16, std::max(1, kn.leaf16.get(ldsn_spheres ? 5 : 3)));
+    // whole wave-loads of ids only (batch_ids): the start ring makes 64 path starts from 64 consecutive ids of a batch.
+    // The 1024-lane LDS-node kernel and the BVH-less list kernels: 1024 ids per atomic (a shorter end-of-frame
     // tail; jumpy-1080p +1.2%, cornell-800 +0.5% over 2048, profiles/r03/experiments k3 / k4); the mesh
     // kernels keep 2048 (neutral on cow; their short paths made small batches costly in round 2)
-    if ((var.k16 && var.block == 1024u) || sc.flat.nodes4.empty())
-      a.batch = batch_ids(env_int("RTW_BATCH", 1024));
+    const bool small_batch = (k.lds_nodes() && k.blk == 1024) || sc.flat.nodes4.empty();
+    a.batch = batch_ids(kn.batch.get(small_batch ? 1024 : (int)dev::BATCH));
     // Regenerate paths only once >= regen_min lanes of a wave are idle (or all are): start_path
     // runs at wave level, so batching it raises its SIMD utilisation.  Measured on MI355X
     // (RTW_REGEN_MIN sweep 1..32): 24 is best for open scenes (jumpy-balls +4.3%, cow +1.6%,
@@ -2827,8 +2910,8 @@ int enqueue_render(Scene& sc, DeviceCopy& c, const rtw_camera* cam, const float 
     // With the start ring (round 6, the rect list kernel) a regeneration costs a few LDS reads, not start_path at
     // the idle lanes' occupancy, so waves refill early: REGEN_RING (cornell-800: 8 -> 2, +1.8%).
     const bool boxed = (sc.flat.features & ~F_SMOKE) == 0;
-    a.regen_min = (uint32_t)std::min(64, std::max(1, env_int("RTW_REGEN_MIN", var.sring ? REGEN_RING : (boxed ? 8 : 24))));
-    const int grid = resident_grid(c, fn, var.block, count);
+    a.regen_min = (uint32_t)std::min(64, std::max(1, kn.regen_min.get(k.sring() ? REGEN_RING : (boxed ? 8 : 24))));
+    const int grid = resident_grid(c, var, count, kn.verbose);
     // Small frames: fewer ids per atomic, halving until every resident wave can take >= 32 batches.  configs[0]
     // (jumpy-balls 400x225x50: 4.5 M paths for 8,192 resident waves) handed out 4,395 batches of 1,024, so half the
     // waves got none and the kernel ran 5x slower per ray than at 1080p: 5.43k -> 9.30k Mrays/s at 128.  The same
@@ -2837,22 +2920,16 @@ int enqueue_render(Scene& sc, DeviceCopy& c, const rtw_camera* cam, const float 
     // word below 512 (cow 256: -16%), the others' below 128.  Full frames keep the defaults (>= 32 batches per
     // wave already); knob RTW_BATCH sets the size outright.
     const uint32_t batch0 = a.batch, batch_floor = batch0 >= 2048u ? 512u : 128u;
-    const bool batch_auto = tuning_env("RTW_BATCH") == nullptr;
-    const uint64_t waves = (uint64_t)grid * var.block / 64u;
+    const bool batch_auto = !kn.batch.set;
+    const uint64_t waves = (uint64_t)grid * (uint32_t)k.blk / 64u;
     // the LDS-node variants walk 16-bit codes within their own stack rows (pick_kernel checked
     // stack_need4 against them) and have no HBM spill path
-    const uint32_t lds = var.stack;
-    a.spill_depth = (!var.k16 && sc.flat.stack_need > lds) ? sc.flat.stack_need - lds : 0;
-    a.spill_lanes = (uint32_t)grid * var.block;
-    const size_t spill_bytes = (size_t)a.spill_depth * a.spill_lanes * sizeof(int32_t);
-    if (spill_bytes > c.spill_bytes) {  // first render of a deep tree only
-      if (c.spill) HIPCHK(hipFree(c.spill), "hipFree(stack spill)");
-      c.spill = nullptr;
-      c.spill_bytes = 0;
-      HIPCHK(hipMalloc((void**)&c.spill, spill_bytes), "hipMalloc(stack spill)");
-      c.spill_bytes = spill_bytes;
-    }
-    a.spill = c.spill;
+    const uint32_t lds = (uint32_t)k.stack;
+    a.spill_depth = (!k.lds_nodes() && sc.flat.stack_need > lds) ? sc.flat.stack_need - lds : 0;
+    a.spill_lanes = (uint32_t)grid * (uint32_t)k.blk;
+    // (first render of a deep tree only)
+    if (int e = grow(c.spill, (size_t)a.spill_depth * a.spill_lanes * sizeof(int32_t))) return e;
+    a.spill = static_cast<int32_t*>(c.spill.p);
     for (uint32_t base = 0; base < n_slots; base += slots_per_pass) {
       const uint32_t ns = std::min(slots_per_pass, n_slots - base);
       a.slot_base = base;
@@ -2868,7 +2945,7 @@ int enqueue_render(Scene& sc, DeviceCopy& c, const rtw_camera* cam, const float 
       if (!ke[0]) HIPCHK(hipEventCreate(&ke[0]), "hipEventCreate");
       if (!ke[1]) HIPCHK(hipEventCreate(&ke[1]), "hipEventCreate");
       HIPCHK(hipEventRecord(ke[0], stream), "hipEventRecord");
-      hipLaunchKernelGGL(fn, dim3(grid), dim3(var.block), 0, stream, a);
+      hipLaunchKernelGGL(var.fn, dim3(grid), dim3(k.blk), 0, stream, a);
       HIPCHK(hipGetLastError(), "path_kernel launch");
       HIPCHK(hipEventRecord(ke[1], stream), "hipEventRecord");
       c.kev_head = (c.kev_head + 1) % 64u;
@@ -2925,13 +3002,6 @@ int rtw_device_count(void) {
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
   return n;
 }
-
-// restores the caller's current device on every return path
-struct DeviceGuard {
-  int prev = 0;
-  DeviceGuard() { hipGetDevice(&prev); }
-  ~DeviceGuard() { hipSetDevice(prev); }
-};
 
 int rtw_render(rtw_scene* s, const rtw_camera* cam, const float bg[3], uint32_t w, uint32_t h,
                uint32_t spp, uint32_t max_depth, uint64_t seed, float* out, rtw_stats* stats) {
@@ -3122,8 +3192,7 @@ int rtw_path_kernel_times(rtw_scene* s, int device, float* ms, uint32_t max_n) {
   if (!s || (!ms && max_n)) return fail(RTW_EINVAL, "NULL argument");
   DeviceCopy* c = find_copy(s->s, device);
   if (!c) return fail(RTW_ENODEV, "scene was not committed to device %d", device);
-  int prev = 0;
-  hipGetDevice(&prev);
+  DeviceGuard g;
   HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
   const uint32_t n = std::min(c->kev_count, max_n);
   int rc = (int)n;
@@ -3139,7 +3208,6 @@ int rtw_path_kernel_times(rtw_scene* s, int device, float* ms, uint32_t max_n) {
   c->kev_count = 0;
   if (rc >= 0 && n)  // the launches waited for: report a tripped traversal guard (its frame is invalid)
     if (int e = check_guard(*c)) rc = e;
-  hipSetDevice(prev);
   return rc;
 }
 

@@ -6,7 +6,7 @@
 #include "rtw_kernel.hip"
 
 namespace rtw {
-Variant pick_mesh(bool count, uint32_t need, bool half, bool codes16) {
-  return count ? pick5<true, F_MESHES>(need, half, codes16) : pick5<false, F_MESHES>(need, half, codes16);
+Variant pick_mesh(bool count, const Knobs& kn, uint32_t need, bool half, bool codes16) {
+  return count ? pick5<true, F_MESHES>(kn, need, half, codes16) : pick5<false, F_MESHES>(kn, need, half, codes16);
 }
 }  // namespace rtw

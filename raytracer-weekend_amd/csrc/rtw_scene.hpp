@@ -101,10 +101,8 @@ struct DeviceCopy {
   // host-mapped sticky error word (hipHostMalloc): a path kernel whose traversal guard trips writes 1;
   // the host reads it at the next render call, rtw_render_status, rtw_path_kernel_times and with stats
   uint32_t* err_host = nullptr;
-  float* sbuf = nullptr;                   // ordered per-sample radiance (rgb per path)
-  uint64_t sbuf_paths = 0;
-  int32_t* spill = nullptr;                // traversal-stack overflow (trees deeper than the LDS stack)
-  size_t spill_bytes = 0;
+  DevBuf sbuf;                             // ordered per-sample radiance (rgb floats per path of a pass)
+  DevBuf spill;                            // traversal-stack overflow (trees deeper than the LDS stack)
   void* kev[64][2] = {};                   // hipEvent_t pairs around path-kernel launches (ring,
                                            // rtw_path_kernel_times)
   uint32_t kev_head = 0, kev_count = 0;
@@ -146,6 +144,9 @@ int upload(Scene& s, int device);
 void release(Scene& s);
 DeviceCopy* find_copy(Scene& s, int device);  // device < 0: the first copy
 int grow(DevBuf& b, size_t bytes);            // current device; contents not kept
+// field 0-7 (stack, spill, occ, feat, blk, ncap, half, s16) of the path-kernel configuration the current
+// environment selects for the committed scene (rtw_scene_info 16-23); host only, no device needed
+int64_t selected_kernel_info(const Scene& s, int field);
 // Which 8x8 tiles a render covers and where they go: slot k renders tile ids[k] (a device array), or
 // tile first + k * stride without one; the output is packed [slot][64][3] when `packed` (always with
 // ids), else the full w x h image.

@@ -16,7 +16,7 @@ SRC = ROOT / "raytracer-weekend_amd" / "csrc" / "rtw_kernel.hip"
 
 
 def _preprocess(*defs):
-    cmd = [HIPCC, "-E", "-x", "hip", "--offload-arch=gfx950", "--cuda-device-only", "-std=c++17",
+    cmd = [HIPCC, "-E", "-x", "hip", "--offload-arch=gfx950", "--cuda-device-only", "-std=c++20",
            "-o", "/dev/null", str(SRC)] + [f"-D{d}" for d in defs]
     return subprocess.run(cmd, capture_output=True, text=True, timeout=300)
 

@@ -6,8 +6,8 @@ family, and the global-node and spill kernels by knob."""
 import numpy as np
 import pytest
 
-from test_gpu_far import BG as FAR_BG, F_MEDIUM, F_SMOKE, H as FAR_H, SEED as FAR_SEED, SPP as FAR_SPP, W as FAR_W, \
-    far_reference, far_world
+from test_gpu_far import BG as FAR_BG, F_ALL, F_BOXES, F_MEDIUM, F_MESHES, F_SMOKE, F_SPHERES, H as FAR_H, \
+    SEED as FAR_SEED, SPP as FAR_SPP, W as FAR_W, far_reference, far_world, selected_kernel
 
 pytestmark = pytest.mark.gpu
 
@@ -19,12 +19,28 @@ PRESETS = {
     "smokey-cornell-box": (1.0, 32, 32, 6, True),       # 8 prims: the all-features list kernel, with media
     "two-perlin-spheres": (16 / 9, 48, 27, 3, True),    # 2 spheres: the all-features list kernel, noise textures
 }
-CASES = [("jumpy-balls", ""), ("jumpy-balls", "RTW_LDS_NODES=0"), ("jumpy-balls", "RTW_STACK_LDS=4"),
-         ("cornell-box", ""), ("cornell-box", "RTW_LIST_ALL=1"),
-         ("wavefront-cow-obj", ""), ("wavefront-cow-obj", "RTW_LDS_NODES=0"), ("wavefront-cow-obj", "RTW_STACK_LDS=4"),
-         ("smokey-cornell-box", ""), ("two-perlin-spheres", ""),
-         ("far:static", ""),   # the far-camera ball field of test_gpu_far.py (trace_far's node visits counted)
-         ("far:smoke", "")]    # that file's rect-and-media BVH: the F_SMOKE kernel (smokey-cornell-box is a list world)
+F_LIST = 1 << 16
+LDSN_1024 = (16, 0, 8, F_SPHERES, 1024, 144, 0, 0)
+MESH_S16 = (30, 0, 7, F_MESHES, 256, 0, 1, 1)
+SPILL_TEST = (4, 1, 4, F_ALL, 256, 0, 0, 0)
+LIST_ALL = (1, 0, 5, F_ALL | F_LIST, 256, 0, 0, 0)
+# (world, knob): the kernel it selects (rtw_scene_info 16-23, see test_gpu_far.py SPHERE_KERNELS)
+KERNELS = {
+    ("jumpy-balls", ""): LDSN_1024,
+    ("jumpy-balls", "RTW_LDS_NODES=0"): (24, 0, 6, F_SPHERES, 256, 0, 0, 0),
+    ("jumpy-balls", "RTW_STACK_LDS=4"): SPILL_TEST,
+    ("cornell-box", ""): (1, 0, 8, F_BOXES | F_LIST, 256, 0, 0, 0),
+    ("cornell-box", "RTW_LIST_ALL=1"): LIST_ALL,
+    ("wavefront-cow-obj", ""): MESH_S16,
+    ("wavefront-cow-obj", "RTW_LDS_NODES=0"): MESH_S16,  # (the knob is the sphere kernels': the cow's kernel stays)
+    ("wavefront-cow-obj", "RTW_STACK_LDS=4"): SPILL_TEST,
+    ("smokey-cornell-box", ""): LIST_ALL,
+    ("two-perlin-spheres", ""): LIST_ALL,
+    ("far:static", ""): LDSN_1024,  # the far-camera ball field of test_gpu_far.py (trace_far's node visits counted)
+    # that file's rect-and-media BVH: the F_SMOKE kernel (smokey-cornell-box is a list world)
+    ("far:smoke", ""): (24, 0, 5, F_SMOKE, 256, 0, 0, 0),
+}
+CASES = list(KERNELS)
 SEED = 11
 _REF = {}  # preset name -> (oracle image, oracle rays): rendered once, shared, never written
 
@@ -67,6 +83,7 @@ def test_count_kernel_renders_and_counts(gpu, orc, knobs, world, knob):
         knobs.setenv(*knob.split("="))
     s, rt, ref, rays, is_list = _world(rtw, orc, world)
     assert (s.info(3) == 0) == is_list
+    assert selected_kernel(s) == KERNELS[(world, knob)]
     if world == "far:smoke":
         assert s.info(9) & ~F_SMOKE == 0 and s.info(14) == 1
     stream = torch.cuda.current_stream().cuda_stream

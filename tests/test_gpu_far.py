@@ -217,28 +217,40 @@ def _knob_preconditions(s, knob, sphere_world):
             assert n_nodes <= 144 and need4 <= 16
 
 
-# The kernel each knob selects for the sphere-only worlds (static, moving), from pick_kernel:
-#   ""                        path_kernel<16, -, 8, F_SPHERES, 1024, 144>       LDS nodes, 16-bit stack, 1024 lanes
-#   RTW_LDS_NODES=0           path_kernel<STACK_LDS5, -, 6, F_SPHERES>          global nodes, 32-bit stack
-#   RTW_HALF_NODES=1          path_kernel<16, -, 8, F_SPHERES, 512, 144, HN>    half nodes in LDS; the far walk reads
-#                                                                               the global f32 table, codes at +112
-#   RTW_LDSN_WAVES=6          path_kernel<24, -, 6, F_SPHERES, 512, 224>
-#   RTW_LDSN_WAVES=7          path_kernel<18, -, 7, F_SPHERES, 448, 160>
-#   RTW_LDSN_BLK=512          path_kernel<16, -, 8, F_SPHERES, 512, 144>
-#   RTW_OCC=5                 pick5<F_SPHERES>: path_kernel<STACK_LDS5, -, 5, F_SPHERES>
-#   RTW_OCC=4                 path_kernel<STACK_LDS, -, 4, F_SPHERES>
-#   RTW_GENERIC=1             the default's kernel: pick_kernel reads RTW_GENERIC only on its default branch, which a
-#                             sphere world (RTW_OCC's default 6) leaves before; kept as the matrix lists it
-#   RTW_GENERIC=1,RTW_OCC=5   pick5<F_ALL>: path_kernel<STACK_LDS5, -, 5, F_ALL>  (the generic kernel, for real)
-#   RTW_STACK_LDS=4           path_kernel<4, SPILL, 4, F_ALL>: a 4-entry column, the far walk's overflow pass
-# and for the rotated world (F_INST: not a sphere world)
-#   ""                        pick5<F_ALL>: path_kernel<STACK_LDS5, -, 5, F_ALL>
-#   RTW_OCC=4                 path_kernel<STACK_LDS, -, 4, F_ALL>
-#   RTW_STACK_LDS=4           path_kernel<4, SPILL, 4, F_ALL>
-SPHERE_KNOBS = ["", "RTW_LDS_NODES=0", "RTW_HALF_NODES=1", "RTW_LDSN_WAVES=6", "RTW_LDSN_WAVES=7", "RTW_LDSN_BLK=512",
-                "RTW_OCC=5", "RTW_OCC=4", "RTW_GENERIC=1", "RTW_GENERIC=1,RTW_OCC=5", "RTW_STACK_LDS=4"]
+# The kernel each knob selects, from pick_kernel, as rtw_scene_info 16-23 report it (KernelCfg: stack rows, HBM spill,
+# waves / SIMD, feature set, workgroup size, node4s of the LDS node table, half nodes, 16-bit stack over global nodes)
+F_ALL = ((1 << 16) - 1) | F_TEXGEN
+SPHERE_KERNELS = {  # the sphere-only worlds (static, moving)
+    "": (16, 0, 8, F_SPHERES, 1024, 144, 0, 0),                  # LDS nodes, 16-bit stack, 1024 lanes
+    "RTW_LDS_NODES=0": (STACK_LDS5, 0, 6, F_SPHERES, 256, 0, 0, 0),  # global nodes, 32-bit stack
+    # half nodes in LDS; the far walk reads the global f32 table, codes at +112
+    "RTW_HALF_NODES=1": (16, 0, 8, F_SPHERES, 512, 144, 1, 0),
+    "RTW_LDSN_WAVES=6": (24, 0, 6, F_SPHERES, 512, 224, 0, 0),
+    "RTW_LDSN_WAVES=7": (18, 0, 7, F_SPHERES, 448, 160, 0, 0),
+    "RTW_LDSN_BLK=512": (16, 0, 8, F_SPHERES, 512, 144, 0, 0),
+    "RTW_OCC=5": (STACK_LDS5, 0, 5, F_SPHERES, 256, 0, 0, 0),    # pick5<F_SPHERES>
+    "RTW_OCC=4": (STACK_LDS, 0, 4, F_SPHERES, 256, 0, 0, 0),
+    # the default's kernel: pick_kernel reads RTW_GENERIC only on its default branch, which a sphere world (RTW_OCC's
+    # default 6) leaves before; kept as the matrix lists it
+    "RTW_GENERIC=1": (16, 0, 8, F_SPHERES, 1024, 144, 0, 0),
+    "RTW_GENERIC=1,RTW_OCC=5": (STACK_LDS5, 0, 5, F_ALL, 256, 0, 0, 0),  # pick5<F_ALL>: the generic kernel, for real
+    "RTW_STACK_LDS=4": (4, 1, 4, F_ALL, 256, 0, 0, 0),           # a 4-entry column, the far walk's overflow pass
+}
+ROTATED_KERNELS = {  # the rotated world (F_INST: not a sphere world)
+    "": (STACK_LDS5, 0, 5, F_ALL, 256, 0, 0, 0),                 # pick5<F_ALL>
+    "RTW_OCC=4": (STACK_LDS, 0, 4, F_ALL, 256, 0, 0, 0),
+    "RTW_STACK_LDS=4": (4, 1, 4, F_ALL, 256, 0, 0, 0),
+}
+
+
+def selected_kernel(s):
+    """rtw_scene_info 16-23: the path-kernel configuration the environment selects for s."""
+    return tuple(s.info(16 + k) for k in range(8))
+
+
+SPHERE_KNOBS = list(SPHERE_KERNELS)
 FAR_MATRIX = [(v, k) for v in ("static", "moving") for k in SPHERE_KNOBS] + \
-             [("rotated", k) for k in ("", "RTW_OCC=4", "RTW_STACK_LDS=4")]
+             [("rotated", k) for k in ROTATED_KERNELS]
 
 
 @pytest.mark.parametrize("variant,knob", FAR_MATRIX)
@@ -253,6 +265,7 @@ def test_far_origin_camera_bit_exact(gpu, orc, knobs, variant, knob):
     s, text, imgs, cam = far_world(rtw, variant)
     assert_far(s)
     _knob_preconditions(s, knob, sphere_world=variant != "rotated")
+    assert selected_kernel(s) == (ROTATED_KERNELS if variant == "rotated" else SPHERE_KERNELS)[knob]
     g, st = rtw.Raytracer(s, cam, BG, W, H, SPP, seed=SEED).render()
     r, rays = far_reference(orc, variant, text, imgs, cam)
     assert_same(g, st["rays"], r, rays)
