@@ -1128,8 +1128,14 @@ __device__ __forceinline__ void trace_begin(const DevScene& S, const Ray& r, Tra
 #ifndef RTW_SRING
 #define RTW_SRING 1  // path starts made a ring of 64 at a time (path_kernel SRING; 0 = each lane's own, for A/B)
 #endif
+#ifndef RTW_SRING_LDSN
+#define RTW_SRING_LDSN 1  // the 1024-lane LDS-node sphere kernel: the ring in place of its state rows (0 = the rows, for A/B)
+#endif
 #ifndef REGEN_RING
 #define REGEN_RING 2  // regen_min of the kernels with the start ring
+#endif
+#ifndef REGEN_RING_LDSN
+#define REGEN_RING_LDSN 8  // ... of the 1024-lane sphere kernel with it (jumpy-1080p: flat from 1 to 16, 8-12 best by 0.2%)
 #endif
 typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ half2_t as_h2(uint32_t u) { return __builtin_bit_cast(half2_t, u); }
@@ -1799,6 +1805,57 @@ __device__ __forceinline__ void fill_start_args(const RenderArgs& a, StartArgs& 
   o.tile_ids = a.tile_ids;
 }
 
+// start_path (below) in two halves, for the start ring's 7-word entry (path_kernel SRING, K.ldsn_ring()): start_make
+// is everything up to the time draw -- the scaled lens sample rd, the direction d and the generator's state before
+// that draw -- and start_take the rest from those: the origin (the lens offset again, from the same operands), the
+// time draw, T, depth and the id.  The same f32 operations on the same inputs as start_path's, so every bit of the
+// start is the same.  (A copy, not start_path's own body: with start_path written as the two halves back to back
+// every other variant's register allocation moved -- VGPRs, scratch and VALU count, scripts/isa_usage.sh.)
+struct StartMade {
+  float rdx, rdy;
+  V3 d;
+  uint64_t rng;
+};
+template <bool FROM_LDS, bool AB>
+__device__ __forceinline__ bool start_make(const StartArgs& a, uint64_t pid, StartMade& m) {
+  if constexpr (FROM_LDS) asm volatile("" ::: "memory");  // read the LDS copy here: no loop-invariant register copies
+  const uint32_t hi = (uint32_t)(pid >> 6), l = (uint32_t)pid & 63u;
+  const uint32_t slot = a.spp > 1u ? fastdiv(hi, a.spp_magic) : hi, s = hi - slot * a.spp;
+  const uint32_t gslot = a.slot_base + slot;
+  const uint32_t tile = a.tile_ids ? a.tile_ids[gslot] : a.tile_first + gslot * a.tile_stride;
+  const uint32_t ty = a.tiles_x > 1u ? fastdiv(tile, a.tiles_x_magic) : tile;
+  const uint32_t i = (tile - ty * a.tiles_x) * 8u + (l & 7u), row = ty * 8u + (l >> 3);
+  // (an off-image id runs through the rest all the same, on a pixel that does not exist, and the caller drops what it
+  // made: the wave makes 64 starts together, and results carried out of a divergent branch were spilled to scratch)
+  const uint32_t j = a.h - 1u - row;
+  const DevCamera& C = a.cam;
+  uint64_t rng = xoro_seed(splitmix64(a.seed_hash ^ (((uint64_t)j << 48) | ((uint64_t)i << 32) | s)));
+  // lib.rs:84-86 + camera.rs:66-74
+  const float u = div_by_recip((float)i + gen_f32(rng), a.fw1, a.rw1);
+  const float v = div_by_recip((float)j + gen_f32(rng), a.fh1, a.rh1);
+  const V3 rd = scale(rand_in_unit_disk<AB>(rng), C.lens_radius);
+  const V3 off = add(scale(ld3(C.u), rd.x), scale(ld3(C.v), rd.y));
+  m.rdx = rd.x;
+  m.rdy = rd.y;
+  m.d = sub(sub(add(add(ld3(C.llc), scale(ld3(C.horizontal), u)), scale(ld3(C.vertical), v)), ld3(C.origin)), off);
+  m.rng = rng;
+  return i < a.w && row < a.h;
+}
+// (FENCE: the ring's take re-reads the LDS copy of the operands, as start_make does)
+template <bool FENCE, bool AB>
+__device__ __forceinline__ void start_take(const StartArgs& a, float rdx, float rdy, uint64_t rng, uint32_t pid,
+                                           PathState& st) {
+  if constexpr (FENCE) asm volatile("" ::: "memory");
+  const DevCamera& C = a.cam;
+  const V3 off = add(scale(ld3(C.u), rdx), scale(ld3(C.v), rdy));
+  st.ray.o = add(ld3(C.origin), off);
+  st.ray.time = gen_range<AB>(rng, C.time0, C.time1, a.time_span);
+  st.rng = rng;
+  st.T = mk(1.f, 1.f, 1.f);
+  st.depth = a.max_depth;
+  st.pid = pid;
+}
+
 // LST_BLK > 0: also store T = 1, depth and the path id in the lane's LDS state rows (path_kernel LST), here
 // where the values are made (carried to the caller, they were spilled)
 template <bool FROM_LDS, int LST_BLK = 0, int LST_ROW = 0, bool AB = FROM_LDS>
@@ -1853,12 +1910,17 @@ struct KernelCfg {
   // the LDS-node kernel (sorted-push walk over the node table in LDS; no HBM spill path)
   constexpr bool lds_nodes() const { return ncap > 0; }
   // LST: the paths' T / depth / id in 10 more 16-bit rows after the stack (the S16 walk's column has stack + 1 rows)
-  constexpr int lst_rows() const { return ((ncap > 0 && blk == 1024) || s16) ? 10 : 0; }
+  // (the 1024-lane LDS-node sphere kernel spends that LDS on the start ring instead: its T / depth / id are in
+  // PathState, as in the 512-lane form; RTW_SRING_LDSN=0 gives it the rows back)
+  constexpr bool ldsn_ring() const { return RTW_SRING && RTW_SRING_LDSN && ncap > 0 && blk == 1024 && feat == F_SPHERES; }
+  constexpr int lst_rows() const { return (((ncap > 0 && blk == 1024) || s16) && !ldsn_ring()) ? 10 : 0; }
   constexpr int lst_row0() const { return stack + (s16 ? 1 : 0); }
   constexpr bool lst() const { return lst_rows() > 0; }
   constexpr bool shard() const { return ncap > 0; }  // SHARD: several path-id dispensers (path_kernel)
-  // SRING: path starts from the wave's ring of 64 (path_kernel; the rect list kernel only)
-  constexpr bool sring() const { return RTW_SRING && feat == (F_BOXES | F_LIST) && !lst(); }
+  // SRING: path starts from the wave's ring of 64 (path_kernel; the rect list kernel and the 1024-lane sphere kernel)
+  constexpr bool sring() const { return (RTW_SRING && feat == (F_BOXES | F_LIST) && !lst()) || ldsn_ring(); }
+  // words per ring entry: the whole start (o, d, time, rng, id), or start_make's half of it where LDS is short
+  constexpr int ring_words() const { return ldsn_ring() ? 7 : 10; }
   // the S16 half-node mesh walk keeps the tree's top RTW_MESH_ROOT node4s in LDS (trace_run ROOT)
   constexpr bool root_lds() const { return half && s16 && ncap == 0 && RTW_MESH_ROOT > 0; }
   constexpr bool alignbit_draws() const { return !(feat & F_TRI); }                // AB: the one-alignbit draws
@@ -1908,7 +1970,8 @@ __global__ __launch_bounds__(K.blk) __attribute__((amdgpu_waves_per_eu(K.occ, 8)
   int32_t* stk = stk_all + threadIdx.x;
   int32_t* spill = a.spill + (size_t)blockIdx.x * K.blk + threadIdx.x;  // unused unless spill_depth > 0
   const uint32_t lane = threadIdx.x & 63u;
-  // LST (1024-lane LDS-node workgroups, 2 per CU: half the node-table copies of 512-lane ones): a path's
+  // LST (the S16 mesh walk; the 1024-lane LDS-node sphere kernel too when built with RTW_SRING_LDSN=0: by default
+  // its start ring has that LDS, at 68 B of scratch per lane instead of 24, profiles/r07/experiments): a path's
   // throughput, remaining depth and id live in LDS, not VGPRs.  At 8 waves / SIMD (64 VGPRs) the compiler
   // spilled exactly these to scratch (a scratch load / store per use in every shading pass: ~40% of the
   // kernel's vector-memory instructions and ~23 GB of HBM write-back per jumpy-1080p frame)
@@ -1974,12 +2037,26 @@ __global__ __launch_bounds__(K.blk) __attribute__((amdgpu_waves_per_eu(K.occ, 8)
   // taken by the lanes that regenerate (start_path is a function of the id alone, so which lane makes a path's start
   // changes nothing).  start_path at full lane occupancy instead of the few idle lanes of each regeneration.
   // Per lane slot: o, d, time, rng (2 words), pid (10 words, structure of arrays); rng = 0 marks an off-image id.
-  // (the rect list kernel only: its LDS is free and its VGPRs hold the generation; the LDS-node and mesh kernels have
-  // no LDS left for 2.5 KB per wave at their occupancy)
-  __shared__ uint32_t ring_lds[K.sring() ? (K.blk / 64) * 640 : 1];
-  __shared__ uint32_t ring_head_lds[K.sring() ? K.blk / 64 : 1];
-  uint32_t* const ring = ring_lds + (K.sring() ? (threadIdx.x >> 6) * 640u : 0u);
-  uint32_t* const ring_head = ring_head_lds + (K.sring() ? threadIdx.x >> 6 : 0u);
+  // (the rect list kernel: its LDS is free and its VGPRs hold the generation.)
+  // The 1024-lane LDS-node sphere kernel (K.ldsn_ring()) has 1.75 KB per wave once its state rows are gone: a 7-word
+  // entry, start_make's half of the start -- rd.x, rd.y, d, rng before the time draw -- and the ring's first id once
+  // per wave (an entry's id is that + its index); the lanes that take an entry finish it with start_take.
+  // (the other LDS-node and the mesh kernels have no LDS left for a ring at their occupancy)
+  // Its head and first id follow the wave's entries (RS words per wave), so one address serves all three.
+  constexpr uint32_t RW = K.ring_words(), RS = RW * 64u + (K.ldsn_ring() ? 2u : 0u);
+  __shared__ uint32_t ring_lds[K.sring() ? (K.blk / 64) * RS : 1];
+  __shared__ uint32_t ring_head_lds[K.sring() && !K.ldsn_ring() ? K.blk / 64 : 1];
+  if constexpr (K.ldsn_ring()) {
+    // 2 workgroups per CU (8 waves / SIMD at 1024 lanes) share its 163,840 B: 81,920 B each.  16 stack rows x 1024 x
+    // 2 B = 32,768 + 144 node4s x 128 B = 18,432 + the ring, 16 waves x 64 entries x 7 words x 4 B = 28,672 + heads and
+    // first ids 128 + pools 640 + StartArgs = 80,808 B (a 10-word entry, or the state rows beside the ring, do not fit)
+    static_assert(sizeof stk_all + sizeof stk16_all + sizeof nodes_lds + sizeof start_lds + sizeof pool_lds +
+                          sizeof ring_lds + sizeof ring_head_lds <= 81920,
+                  "the 1024-lane ring kernel's LDS must leave room for 2 workgroups per CU");
+  }
+  uint32_t* const ring = ring_lds + (K.sring() ? (threadIdx.x >> 6) * RS : 0u);
+  uint32_t* const ring_head = K.ldsn_ring() ? ring + RW * 64u : ring_head_lds + (K.sring() ? threadIdx.x >> 6 : 0u);
+  uint32_t* const ring_base = ring + (K.ldsn_ring() ? RW * 64u + 1u : 0u);  // (K.ldsn_ring() only)
   if (K.sring() && lane == 0) ring_head[0] = 64u;
   bool exhausted = false;                // wave-uniform
   bool has = false;
@@ -2014,16 +2091,25 @@ __global__ __launch_bounds__(K.blk) __attribute__((amdgpu_waves_per_eu(K.occ, 8)
         uint32_t head = (uint32_t)__builtin_amdgcn_readfirstlane((int)ring_head[0]);
         const uint32_t have = 64u - head;
         auto take = [&](uint32_t e) {
-          const uint32_t lo = ring[7 * 64 + e], hi = ring[8 * 64 + e];
-          st.ray.o = mk(__uint_as_float(ring[e]), __uint_as_float(ring[64 + e]), __uint_as_float(ring[2 * 64 + e]));
-          st.ray.d = mk(__uint_as_float(ring[3 * 64 + e]), __uint_as_float(ring[4 * 64 + e]),
-                        __uint_as_float(ring[5 * 64 + e]));
-          st.ray.time = __uint_as_float(ring[6 * 64 + e]);
-          st.rng = ((uint64_t)hi << 32) | lo;
-          st.pid = ring[9 * 64 + e];
-          st.T = mk(1.f, 1.f, 1.f);
-          st.depth = SA.max_depth;
-          has = (lo | hi) != 0u;
+          if constexpr (K.ldsn_ring()) {  // the 7-word entry: start_take finishes it
+            const uint32_t lo = ring[5 * 64 + e], hi = ring[6 * 64 + e];
+            const float rdx = __uint_as_float(ring[e]), rdy = __uint_as_float(ring[64 + e]);
+            st.ray.d = mk(__uint_as_float(ring[2 * 64 + e]), __uint_as_float(ring[3 * 64 + e]),
+                          __uint_as_float(ring[4 * 64 + e]));
+            start_take<true, K.alignbit_draws()>(SA, rdx, rdy, ((uint64_t)hi << 32) | lo, ring_base[0] + e, st);
+            has = (lo | hi) != 0u;
+          } else {
+            const uint32_t lo = ring[7 * 64 + e], hi = ring[8 * 64 + e];
+            st.ray.o = mk(__uint_as_float(ring[e]), __uint_as_float(ring[64 + e]), __uint_as_float(ring[2 * 64 + e]));
+            st.ray.d = mk(__uint_as_float(ring[3 * 64 + e]), __uint_as_float(ring[4 * 64 + e]),
+                          __uint_as_float(ring[5 * 64 + e]));
+            st.ray.time = __uint_as_float(ring[6 * 64 + e]);
+            st.rng = ((uint64_t)hi << 32) | lo;
+            st.pid = ring[9 * 64 + e];
+            st.T = mk(1.f, 1.f, 1.f);
+            st.depth = SA.max_depth;
+            has = (lo | hi) != 0u;
+          }
         };
         const bool first = !has && rank < have;
         if (first) take(head + rank);
@@ -2043,18 +2129,31 @@ __global__ __launch_bounds__(K.blk) __attribute__((amdgpu_waves_per_eu(K.occ, 8)
           // enqueue_render; the automatic halving stays on powers of two >= 128) and n_paths = slots x 64 x spp
           if (pool_next < pool_end) {
             const uint64_t id = pool_next + lane;
-            PathState g;
-            const bool ok = start_path<K.start_args_in_lds(), 0, 0, K.alignbit_draws()>(SA, id, g);
-            ring[lane] = __float_as_uint(g.ray.o.x);
-            ring[64 + lane] = __float_as_uint(g.ray.o.y);
-            ring[2 * 64 + lane] = __float_as_uint(g.ray.o.z);
-            ring[3 * 64 + lane] = __float_as_uint(g.ray.d.x);
-            ring[4 * 64 + lane] = __float_as_uint(g.ray.d.y);
-            ring[5 * 64 + lane] = __float_as_uint(g.ray.d.z);
-            ring[6 * 64 + lane] = __float_as_uint(g.ray.time);
-            ring[7 * 64 + lane] = ok ? (uint32_t)g.rng : 0u;
-            ring[8 * 64 + lane] = ok ? (uint32_t)(g.rng >> 32) : 0u;
-            ring[9 * 64 + lane] = (uint32_t)id;
+            if constexpr (K.ldsn_ring()) {
+              StartMade m;
+              const bool ok = start_make<K.start_args_in_lds(), K.alignbit_draws()>(SA, id, m);
+              ring[lane] = __float_as_uint(m.rdx);
+              ring[64 + lane] = __float_as_uint(m.rdy);
+              ring[2 * 64 + lane] = __float_as_uint(m.d.x);
+              ring[3 * 64 + lane] = __float_as_uint(m.d.y);
+              ring[4 * 64 + lane] = __float_as_uint(m.d.z);
+              ring[5 * 64 + lane] = ok ? (uint32_t)m.rng : 0u;
+              ring[6 * 64 + lane] = ok ? (uint32_t)(m.rng >> 32) : 0u;
+              if (lane == 0) ring_base[0] = (uint32_t)pool_next;
+            } else {
+              PathState g;
+              const bool ok = start_path<K.start_args_in_lds(), 0, 0, K.alignbit_draws()>(SA, id, g);
+              ring[lane] = __float_as_uint(g.ray.o.x);
+              ring[64 + lane] = __float_as_uint(g.ray.o.y);
+              ring[2 * 64 + lane] = __float_as_uint(g.ray.o.z);
+              ring[3 * 64 + lane] = __float_as_uint(g.ray.d.x);
+              ring[4 * 64 + lane] = __float_as_uint(g.ray.d.y);
+              ring[5 * 64 + lane] = __float_as_uint(g.ray.d.z);
+              ring[6 * 64 + lane] = __float_as_uint(g.ray.time);
+              ring[7 * 64 + lane] = ok ? (uint32_t)g.rng : 0u;
+              ring[8 * 64 + lane] = ok ? (uint32_t)(g.rng >> 32) : 0u;
+              ring[9 * 64 + lane] = (uint32_t)id;
+            }
             pool_next += 64u;
             if (!has && !first) take(rank - have);
             head = n_need - have;
@@ -2177,6 +2276,7 @@ __global__ __launch_bounds__(K.blk) __attribute__((amdgpu_waves_per_eu(K.occ, 8)
           atomicMax(dispenser, (unsigned long long)P);
         }
         pool[0] = pool[1];
+        if constexpr (K.ldsn_ring()) ring_head[0] = 64u;  // and its ring of starts
       }
     } else {
       // the prim's shading record is loaded as soon as the winner is known, beside its geometry
@@ -2458,8 +2558,9 @@ constexpr KernelCfg LDSN_224{.stack = 24, .spill = false, .occ = 6, .feat = F_SP
 constexpr KernelCfg LDSN_512{.stack = 16, .spill = false, .occ = 8, .feat = F_SPHERES, .blk = 512, .ncap = 144};
 constexpr KernelCfg LDSN_448{.stack = 18, .spill = false, .occ = 7, .feat = F_SPHERES, .blk = 448, .ncap = 160};
 // 1024-lane workgroups x 2 per CU (knob RTW_LDSN_BLK, 512 = the 4 x 512 form): one node table per 16
-// waves, and the LDS this frees holds the paths' T / depth / id (path_kernel LST) that the 64-VGPR
-// budget otherwise spills to scratch.  LDS per workgroup: 18 KB nodes + 32 KB stack + 20 KB state.
+// waves, and the LDS this frees holds the waves' start rings (path_kernel SRING, KernelCfg::ldsn_ring).  LDS per
+// workgroup: 18 KB nodes + 32 KB stack + 28 KB rings.  (Until round 7 it held the paths' T / depth / id, 20 KB of
+// state rows, path_kernel LST: fewer scratch spills, throughput unchanged; RTW_SRING_LDSN=0 builds that form.)
 constexpr KernelCfg LDSN_1024{.stack = 16, .spill = false, .occ = 8, .feat = F_SPHERES, .blk = 1024, .ncap = 144};
 // The mesh walk with 16-bit stack entries (the nodes' codes: half the LDS of the 32-bit stack, whose 31 KB per
 // workgroup allow 5 per CU) and the paths' T / depth / id in LDS state rows, at 6 or 7 waves / SIMD (knob
@@ -2908,9 +3009,12 @@ int enqueue_render(Scene& sc, DeviceCopy& c, const rtw_camera* cam, const float 
     // monument +1.7% over 1); closed boxes (cornell: 6.6 segments per path, few lanes finish per
     // iteration) lose with deep deferral: 8 (cornell list variant at 8 waves/SIMD: 29.3k at 1, 29.4k at 4, 29.8k at 8, 28.1k at 24).
     // With the start ring (round 6, the rect list kernel) a regeneration costs a few LDS reads, not start_path at
-    // the idle lanes' occupancy, so waves refill early: REGEN_RING (cornell-800: 8 -> 2, +1.8%).
+    // the idle lanes' occupancy, so waves refill early: REGEN_RING (cornell-800: 8 -> 2, +1.8%).  The 1024-lane
+    // sphere kernel's take finishes the start (start_take) and its paths are shorter: REGEN_RING_LDSN
+    // (profiles/r07/experiments).
     const bool boxed = (sc.flat.features & ~F_SMOKE) == 0;
-    a.regen_min = (uint32_t)std::min(64, std::max(1, kn.regen_min.get(k.sring() ? REGEN_RING : (boxed ? 8 : 24))));
+    const int regen_dflt = k.ldsn_ring() ? REGEN_RING_LDSN : (k.sring() ? REGEN_RING : (boxed ? 8 : 24));
+    a.regen_min = (uint32_t)std::min(64, std::max(1, kn.regen_min.get(regen_dflt)));
     const int grid = resident_grid(c, var, count, kn.verbose);
     // Small frames: fewer ids per atomic, halving until every resident wave can take >= 32 batches.  configs[0]
     // (jumpy-balls 400x225x50: 4.5 M paths for 8,192 resident waves) handed out 4,395 batches of 1,024, so half the
