@@ -340,7 +340,7 @@ int rtw_scene_image(const rtw_scene* s, uint32_t k, const uint8_t** rgb8, uint32
  * ordered bounds), 14 1 if the BVH holds sphere tests (their leaves are padded for origins within D0
  * and farther origins take the far-origin walk), 15 that D0 in thousandths, 16-23 the
  * configuration of the path kernel that the current environment (the RTW_* tuning knobs) selects for this
- * scene (csrc/rtw_kernel.hip KernelCfg): 16 LDS stack rows, 17 1 with the HBM stack spill, 18 waves per
+ * scene (csrc/rtw_path_kernel.hpp KernelCfg): 16 LDS stack rows, 17 1 with the HBM stack spill, 18 waves per
  * SIMD, 19 feature set, 20 workgroup size, 21 node4s of the LDS node table, 22 1 with half-precision
  * nodes, 23 1 for the 16-bit stack over global nodes.  3-23 are valid once rtw_scene_commit has flattened
  * the scene (also when its upload failed for lack of a device). */

@@ -184,7 +184,7 @@ static inline vec3 rand_in_unit_disk(draws* d) {
  * differ again, so the reference's exact bits are platform-defined.  This build defines them as
  * the CORRECTLY ROUNDED values: each function is evaluated in double precision with a
  * polynomial of error < 2^-60 and rounded once to f32.  Only IEEE double +,-,*,/,sqrt and floor
- * are used (no FMA contraction), so the GPU kernel (rtw_kernel.hip, same algorithm) produces
+ * are used (no FMA contraction), so the GPU kernel (rtw_dev_math.hpp, same algorithm) produces
  * the same bits.  tests/test_libm.py pins these against (float)glibc-double exhaustively
  * over the ranges the render path reaches; tests/test_gpu_parity.py pins GPU == oracle. */
 static inline uint64_t d2u(double d) { uint64_t u; memcpy(&u, &d, 8); return u; }

@@ -1,5 +1,5 @@
 // rtw_device.hpp — flattened scene layout in HBM, shared by the host flattener
-// (rtw_flatten.cpp) and the gfx950 kernels (rtw_kernel.hip).  Plain PODs only.
+// (rtw_flatten.cpp) and the gfx950 kernels (rtw_kernel.hip and the device headers).  Plain PODs only.
 //
 // Layout (DESIGN.md §Data layout):
 //   nodes   : DevNode[]   BVH2, 64 B per node = both children's boxes + child refs,
@@ -45,7 +45,7 @@ struct alignas(16) DevPrim {
 static_assert(sizeof(DevPrim) == 64, "DevPrim must be 64 B");
 
 // A run of consecutive always-tested prims with one wrapper chain and one PrimType: the list-mode rect loop walks
-// these (no per-prim chain check or type dispatch; rtw_kernel.hip trace_rect_list)
+// these (no per-prim chain check or type dispatch; rtw_dev_trace.hpp trace_rect_list)
 struct alignas(16) DevGroup {
   uint32_t first, count, inst, type;
 };

@@ -784,7 +784,7 @@ int flatten(Scene& s) {
     f.prims.push_back(L.p);
   }
   if (f.depth > MAX_DEPTH) return fail(RTW_EINVAL, "BVH deeper than the traversal stack (%u)", f.depth);
-  // the list-mode rect loop (rtw_kernel.hip trace_rect_list) accepts t <= best: a later prim of the list must
+  // the list-mode rect loop (rtw_dev_trace.hpp trace_rect_list) accepts t <= best: a later prim of the list must
   // have the larger DFS key, which holds because list mode keeps the leaves in walk (= key) order
   if (f.nodes.empty())
     for (size_t k = 1; k < f.always.size(); ++k)
@@ -802,7 +802,7 @@ int flatten(Scene& s) {
       }
     f.tshade.swap(by_prim);
   }
-  // the list-mode rect loop's fast path (rtw_kernel.hip trace_rect_list) divides by Markstein's correction, exact
+  // the list-mode rect loop's fast path (rtw_dev_trace.hpp trace_rect_list) divides by Markstein's correction, exact
   // where |k - o| < 2^64: |o| < 2^62 per lane (checked by the kernel) and |k| < 2^62 for every rect plane (here);
   // and it tests the bounds as med3(x, a0, a1) == x, the reference's !(x < a0 || x > a1) for finite x when
   // a0 <= a1 (here; NaN bounds fail it too)

@@ -1,0 +1,67 @@
+# Is the device code of two revisions the same, kernel by kernel?  (host-side, no GPU): bash scripts/isa_diff.sh REV_A REV_B
+# Checks both revisions out as git worktrees under a temp dir, compiles each kernel unit (csrc/rtw_kernel.hip with the
+# Makefile's HIPFLAGS, csrc/rtw_kernel_mesh.hip with HIPFLAGS_MESH) to device assembly, cuts the assembly at the kernel
+# symbols and pairs the kernels by mangled name, so their order in the code object does not matter.  A kernel's text
+# runs from its "Begin function" line to the next one: the instruction stream, the .amdhsa_kernel block and the
+# resource comments.  Normalised before the comparison, and nothing else: the per-compilation __hip_cuid_<hash> symbol
+# and the per-unit function index in local labels (.LBB<fn>_<n> and the loop comments' BB<fn>_<n>, .Lfunc_end<fn>,
+# .Ltmp<n>), with the padding in front of a comment, which moves with a label's length.
+# Prints "identical N/N" per unit, or the first differing kernel and the head of its diff; exit status 1 if any differs.
+set -e
+[ $# -eq 2 ] || { echo "usage: $0 REV_A REV_B" >&2; exit 2; }
+ROOT="$(git -C "$(dirname "$0")" rev-parse --show-toplevel)"
+TMP="$(mktemp -d)"
+trap 'git -C "$ROOT" worktree remove --force "$TMP/a" 2>/dev/null; git -C "$ROOT" worktree remove --force "$TMP/b" 2>/dev/null; rm -rf "$TMP"' EXIT
+for side in a b; do
+  rev="$1"; [ $side = b ] && rev="$2"
+  git -C "$ROOT" worktree add --detach "$TMP/$side" "$rev" >/dev/null 2>&1
+  pkg="$TMP/$side/raytracer-weekend_amd"
+  hipcc="$(make -s -C "$pkg" --eval 'p-%: ; @echo $($*)' p-HIPCC)"
+  main="$(make -s -C "$pkg" --eval 'p-%: ; @echo $($*)' p-HIPFLAGS)"
+  mesh="$(make -s -C "$pkg" --eval 'p-%: ; @echo $($*)' p-HIPFLAGS_MESH)"
+  (cd "$pkg" && $hipcc $main --offload-device-only -S csrc/rtw_kernel.hip -o "$TMP/$side.main.s") &
+  (cd "$pkg" && $hipcc $mesh --offload-device-only -S csrc/rtw_kernel_mesh.hip -o "$TMP/$side.mesh.s") &
+done
+wait
+python3 - "$TMP" "$1" "$2" <<'PY'
+import difflib, re, sys
+tmp, rev_a, rev_b = sys.argv[1:4]
+
+def kernels(path):
+    txt = open(path).read()
+    txt = txt[:txt.index('\t.section\t.AMDGPU.gpr_maximums')]
+    out = {}
+    parts = re.split(r'^(?=\t\.protected\t\S+ +; -- Begin function )', txt, flags=re.M)
+    for p in parts[1:]:
+        name = p.split()[1]
+        p = re.sub(r'__hip_cuid_[0-9a-f]+', '__hip_cuid_', p)
+        p = re.sub(r'\.(Lfunc_begin|Lfunc_end)\d+', r'.\1', p)
+        p = re.sub(r'(?<![0-9A-Za-z_])(\.L)?BB\d+_(?=\d)', r'\1BB_', p)  # labels, and the loop comments that cite them
+        p = re.sub(r'[ \t]+;', ' ;', p)  # (a longer label shifts the comment column)
+        tmps = {}
+        p = re.sub(r'\.Ltmp\d+', lambda m: tmps.setdefault(m.group(0), '.Ltmp#%d' % len(tmps)), p)
+        # not the kernel's: the section directive of whichever function follows it, and the unit's one end-of-code
+        # padding (.p2alignl / .fill), which lands behind whichever kernel comes last in .text
+        out[name] = [l for l in p.splitlines()
+                     if not l.startswith(('\t.section\t.text', '\t.text', '\t.p2alignl ', '\t.fill '))]
+    return out
+
+bad = 0
+for unit in ('main', 'mesh'):
+    a, b = kernels(f'{tmp}/a.{unit}.s'), kernels(f'{tmp}/b.{unit}.s')
+    n_kern = sum(1 for v in a.values() if any(l.startswith('\t.amdhsa_kernel ') for l in v))
+    if set(a) != set(b):
+        bad = 1
+        for n in sorted(set(a) ^ set(b)):
+            print(f'{unit} unit: {n} only in {rev_a if n in a else rev_b}')
+        continue
+    diff = next((n for n in a if a[n] != b[n]), None)
+    if diff is None:
+        print(f'{unit} unit: identical {len(a)}/{len(a)} ({n_kern} kernels, {sum(map(len, a.values()))} lines)')
+        continue
+    bad = 1
+    same = sum(a[n] == b[n] for n in a)
+    print(f'{unit} unit: identical {same}/{len(a)}; first differing kernel: {diff}')
+    print('\n'.join(list(difflib.unified_diff(a[diff], b[diff], rev_a, rev_b, lineterm='', n=1))[:40]))
+sys.exit(bad)
+PY

@@ -3,7 +3,7 @@
 The reference's f32 sphere test (spherical.rs:26-44) cancels in hb² - a·c: a ray whose origin is D away from a
 sphere "hits" it up to ~sqrt(3u)·D outside its surface, and the flat list (hittable/mod.rs:57-69) finds every such
 hit.  The GPU's BVH pads its sphere leaves for origins within D0 of the BVH and sends farther rays through the
-far-origin walk (rtw_kernel.hip trace_begin / trace_far).  These tests put the origin where the bound matters:
+far-origin walk (rtw_dev_trace.hpp trace_begin / trace_far).  These tests put the origin where the bound matters:
 inside the r = 1000 ground sphere, under a field of small balls, bit for bit against the oracle with equal ray
 counts; and the three random worlds of round 5's 3,000-seed run at 64x36x4 that the padded boxes alone missed.
 
@@ -26,7 +26,7 @@ F_SPHERES = F_SPHERE | F_MSPHERE | F_CHECKER | F_LAMBERT | F_METAL | F_DIEL | F_
 F_BOXES = F_RECT | F_INST | F_LAMBERT | F_METAL | F_DIEL | F_LIGHT
 F_SMOKE = F_BOXES | F_MEDIUM | F_ISO
 F_MESHES = F_SPHERE | F_RECT | F_TRI | F_INST | F_CHECKER | F_IMAGE | F_LAMBERT | F_LIGHT | F_TEXGEN
-# rtw_kernel.hip: rows of the 32-bit LDS stack at 4 waves / SIMD and at 5-6 (STACK_LDS, STACK_LDS5)
+# rtw_dev_math.hpp: rows of the 32-bit LDS stack at 4 waves / SIMD and at 5-6 (STACK_LDS, STACK_LDS5)
 STACK_LDS, STACK_LDS5 = 32, 24
 
 BG = (0.7, 0.8, 1.0)
@@ -63,7 +63,7 @@ def _ball_field(rtw, s, rng, n=14, moving=True, rotated=False):
 def _mesh_world(rtw, s, rng):
     """A mesh world with spheres in its BVH: the checkered ground, 64 Lambertian 0.2 balls and a tilted, tessellated
     quad of 72 triangles lying among them.  Every feature is one of F_MESHES, so but for the far rule
-    (rtw_kernel.hip pick_kernel: `if (far) return pick5<C, F_ALL>(need)`) this world would run the mesh kernels,
+    (rtw_kernel.hip pick_kernel: `if (far) return pick5<F_ALL>(kn, need)`) this world would run the mesh kernels,
     which have no far path."""
     ground = s.lambertian(s.checker(s.solid_rgb(0.2, 0.3, 0.1), s.solid_rgb(0.9, 0.9, 0.9), 10.0))
     s.sphere((0, -1000, 0), 1000, ground)

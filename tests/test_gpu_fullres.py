@@ -6,7 +6,7 @@ Each config renders at its real resolution and camera (bench.py's CONFIGS: jumpy
 packed output); the oracle renders the same rows with the flat-list closest hit of
 hittable/mod.rs:57-69 (a BvhNode group evaluated as the list of its leaves: set semantics).  The
 sums must be bit-identical and the ray counts equal: this pins the kernel's BVH culling (padded
-boxes, relative t slack, rcp slab test: rtw_flatten.cpp, rtw_kernel.hip trace_run) on the
+boxes, relative t slack, rcp slab test: rtw_flatten.cpp, rtw_dev_trace.hpp trace_run) on the
 headline frames, not only on the small parity images.
 """
 import os

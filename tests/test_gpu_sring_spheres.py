@@ -1,4 +1,4 @@
-"""The start ring of the 1024-lane LDS-node sphere kernel (rtw_kernel.hip path_kernel SRING,
+"""The start ring of the 1024-lane LDS-node sphere kernel (rtw_path_kernel.hpp path_kernel SRING,
 KernelCfg::ldsn_ring).
 
 Each wave of that kernel makes 64 path starts at a time from 64 consecutive ids of its pool -- start_make's half of a

@@ -1,4 +1,5 @@
-"""Which path kernel a world and a knob set select (rtw_kernel.hip pick_kernel / pick5 / pick_mesh), asserted.
+"""Which path kernel a world and a knob set select (rtw_kernel.hip pick_kernel, rtw_variants.hpp pick5,
+rtw_kernel_mesh.hip pick_mesh), asserted.
 
 rtw_scene_info 16-23 report the KernelCfg that the current environment selects for a committed scene; no device is
 needed.  The table below was recorded from the commit before the selection code was restructured (that commit plus
