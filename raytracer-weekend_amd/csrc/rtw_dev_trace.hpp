@@ -191,10 +191,13 @@ __device__ __forceinline__ const DevFar* far_record(const DevScene& S) {
   asm volatile("" : "+s"(p));
   return reinterpret_cast<const DevFar*>(p - DEVFAR_BACK);
 }
-__device__ __forceinline__ float far_inv(float d) {  // trace_run's reciprocal (culling only)
+// The walks' culling arithmetic (conservative, never the answer): the reciprocal of a direction component, kept
+// finite, and the far limit of a box test, the best hit's t with slack
+__device__ __forceinline__ float cull_inv(float d) {
   const float dd = fabsf(d) > 1e-20f ? d : copysignf(1e-20f, d);
   return __builtin_amdgcn_rcpf(dd);
 }
+__device__ __forceinline__ float cull_tmax(float t) { return __builtin_fmaf(t, 1.0e-5f, t) + 1.0e-5f; }
 template <bool COUNT, uint32_t FEAT, int STACK, int BLK, bool C16, int NCAP>
 __device__ void trace_far(const DevScene& S, const Ray& r, Best& b, float delta, uint16_t* stk16, int32_t* stk,
                           uint32_t* cnt, uint64_t seg, uint32_t* err, const float4* lnodes) {
@@ -203,7 +206,7 @@ __device__ void trace_far(const DevScene& S, const Ray& r, Best& b, float delta,
   const char* const NB = NCAP > 0 ? reinterpret_cast<const char*>(lnodes)
                                   : reinterpret_cast<const char*>(S.prims) - uload(&FR->nodes_back);
   const uint32_t n_bvh = uload(&FR->n_bvh);
-  const V3 inv = mk(far_inv(r.d.x), far_inv(r.d.y), far_inv(r.d.z));
+  const V3 inv = mk(cull_inv(r.d.x), cull_inv(r.d.y), cull_inv(r.d.z));
   const V3 ood = mk(r.o.x * inv.x, r.o.y * inv.y, r.o.z * inv.z);
   // every box grown by delta: its near plane delta |inv| earlier, its far plane delta |inv| later
   const V3 bn = mk(-ood.x - delta * fabsf(inv.x), -ood.y - delta * fabsf(inv.y), -ood.z - delta * fabsf(inv.z));
@@ -230,7 +233,7 @@ __device__ void trace_far(const DevScene& S, const Ray& r, Best& b, float delta,
     const float4 qnz = *reinterpret_cast<const float4*>(NB + (nb + nz)), qfz = *reinterpret_cast<const float4*>(NB + (nb + fz));
     // 16-bit codes (0 = empty) or the 32-bit child words (0 = empty: the root is nobody's child)
     const uint4 cw = *reinterpret_cast<const uint4*>(NB + (nb + (C16 ? 112u : 96u)));
-    const float tmax_c = __builtin_fmaf(b.t, 1.0e-5f, b.t) + 1.0e-5f;
+    const float tmax_c = cull_tmax(b.t);
     const float NX[4] = {qnx.x, qnx.y, qnx.z, qnx.w}, FX[4] = {qfx.x, qfx.y, qfx.z, qfx.w};
     const float NY[4] = {qny.x, qny.y, qny.z, qny.w}, FY[4] = {qfy.x, qfy.y, qfy.z, qfy.w};
     const float NZ[4] = {qnz.x, qnz.y, qnz.z, qnz.w}, FZ[4] = {qfz.x, qfz.y, qfz.z, qfz.w};
@@ -361,7 +364,7 @@ __device__ __forceinline__ void trace_begin(const DevScene& S, const Ray& r, Tra
           const float az = (-hz - oz) * iz, bz = (hz - oz) * iz;
           const float tn = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fmaxf(fminf(az, bz), 0.0f));
           const float tf = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)),
-                                 fminf(fmaxf(az, bz), __builtin_fmaf(ts.b.t, 1.0e-5f, ts.b.t) + 1.0e-5f));
+                                 fminf(fmaxf(az, bz), cull_tmax(ts.b.t)));
           need = tn <= tf;
         }
         walk = !far;
@@ -454,11 +457,7 @@ __device__ void trace_run(const DevScene& S, const Ray& r, TraceState& ts, int32
       tm = t;
     }
   };
-  auto safe_inv = [](float d) {
-    float dd = fabsf(d) > 1e-20f ? d : copysignf(1e-20f, d);
-    return __builtin_amdgcn_rcpf(dd);
-  };
-  const V3 inv = mk(safe_inv(r.d.x), safe_inv(r.d.y), safe_inv(r.d.z));
+  const V3 inv = mk(cull_inv(r.d.x), cull_inv(r.d.y), cull_inv(r.d.z));
   const V3 ood = mk(r.o.x * inv.x, r.o.y * inv.y, r.o.z * inv.z);
   // near / far plane byte offsets inside DevNode4 by the ray's direction signs (32-bit offsets
   // from the uniform table base: the loads take the SGPR-base + VGPR-offset form)
@@ -500,7 +499,7 @@ __device__ void trace_run(const DevScene& S, const Ray& r, TraceState& ts, int32
           cnt[0]++;
           cnt[14] += (CW[0] != 0) + (CW[1] != 0) + (CW[2] != 0) + (CW[3] != 0);
         }
-        const float tmax_c = __builtin_fmaf(ts.b.t, 1.0e-5f, ts.b.t) + 1.0e-5f;
+        const float tmax_c = cull_tmax(ts.b.t);
         int32_t next = -1, bk = -1;
         float best = INFINITY;
         bool hit[4];
@@ -654,7 +653,7 @@ __device__ void trace_run(const DevScene& S, const Ray& r, TraceState& ts, int32
           simd_tick(cnt, 8, 9);
           cnt[14] += (CW[0] != 0) + (CW[1] != 0) + (CW[2] != 0) + (CW[3] != 0);  // child word 0 = empty slot
         }
-        const float tmax_c = __builtin_fmaf(ts.b.t, 1.0e-5f, ts.b.t) + 1.0e-5f;
+        const float tmax_c = cull_tmax(ts.b.t);
         float tn[4];
         bool hit[4];
 #pragma unroll

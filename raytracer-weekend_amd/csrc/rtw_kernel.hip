@@ -1,7 +1,9 @@
-// rtw_kernel.hip — the host side of the gfx950 path-tracing megakernel and the device half of the C-ABI: the kernels
-// that are no templates (reduce_kernel, unpack_tiles_kernel, the libm and reciprocal diagnostics), the tuning knobs,
-// pick_kernel (which path-kernel variant a scene runs), upload, launch and statistics.  The device code is in headers
-// that this unit and rtw_kernel_mesh.hip (the F_MESHES variants, under their own compiler flags) both include.
+// rtw_kernel.hip — what of the gfx950 path-tracing megakernel's host side needs the device compiler: the kernels
+// that are no templates (reduce_kernel, unpack_tiles_kernel, the libm and reciprocal diagnostics, with the two calls
+// that launch the latter), the tuning knobs, pick_kernel (which path-kernel variant a scene runs) and the launches
+// (enqueue_render, enqueue_unpack).  The scene's device copies, statistics and the render entry points are plain HIP
+// runtime code in rtw_render.cpp.  The device code is in headers that this unit and rtw_kernel_mesh.hip (the F_MESHES
+// variants, under their own compiler flags) both include.
 //
 // Hot path restated (reference raytracer_weekend_lib/src/):
 //   Raytracer::render / sample_pixel (lib.rs:57-95)   -> one work unit per path (pixel, sample); the samples
@@ -45,7 +47,6 @@
 #include <string.h>
 
 #include <algorithm>
-#include <chrono>
 
 #include "../../include/rtw.h"
 #include "rtw_scene.hpp"
@@ -139,153 +140,6 @@ __global__ void sweep_kernel(int fn, uint32_t lo, uint32_t hi, unsigned long lon
 }  // namespace dev
 
 // ---------------------------------------------------------------- host side
-static int hip_fail(hipError_t e, const char* what) {
-  return fail(RTW_ENODEV, "%s: %s", what, hipGetErrorString(e));
-}
-#define HIPCHK(x, what)                          \
-  do {                                           \
-    hipError_t e_ = (x);                         \
-    if (e_ != hipSuccess) return hip_fail(e_, what); \
-  } while (0)
-
-// restores the caller's current device on every return path
-struct DeviceGuard {
-  int prev = 0;
-  DeviceGuard() { hipGetDevice(&prev); }
-  ~DeviceGuard() { hipSetDevice(prev); }
-};
-
-template <class T>
-static size_t put(std::vector<uint8_t>& blob, const std::vector<T>& v) {
-  size_t off = (blob.size() + 255) & ~(size_t)255;
-  blob.resize(off + sizeof(T) * v.size());
-  if (!v.empty()) memcpy(blob.data() + off, v.data(), sizeof(T) * v.size());
-  return off;
-}
-
-int upload(Scene& s, int device) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(RTW_ENODEV, "no HIP device visible (the render core has no CPU fallback)");
-  const int nlog = s.alias_n > 0 ? s.alias_n : ndev;  // logical devices (rtw_diag_alias_devices: all on 0)
-  if (device >= nlog) return fail(RTW_EINVAL, "device %d >= device count %d", device, nlog);
-  const Flat& f = s.flat;
-  std::vector<uint8_t> blob;
-  // the far-origin record sits DEVFAR_BACK bytes before the prim table (trace_begin derives it from S.prims)
-  DevFar far = f.far;
-  const size_t o_nodes = put(blob, f.nodes4), o_far = put(blob, std::vector<DevFar>{far});
-  size_t o_prims = put(blob, f.prims), o_always = put(blob, f.always);
-  if (o_prims - o_far != DEVFAR_BACK) return fail(RTW_EINVAL, "internal: far record not %u B before the prims", DEVFAR_BACK);
-  reinterpret_cast<DevFar*>(blob.data() + o_far)->nodes_back = (uint32_t)(o_prims - o_nodes);
-  size_t o_tsh = put(blob, f.tshade), o_inst = put(blob, f.insts), o_mat = put(blob, f.mats);
-  size_t o_tex = put(blob, f.texs), o_texel = put(blob, f.texels), o_perlin = put(blob, f.perlins);
-  size_t o_shade = put(blob, f.shade), o_hnodes = put(blob, f.nodes4h), o_groups = put(blob, f.lgroups);
-  blob.resize((blob.size() + 255) & ~(size_t)255);
-  int d0 = device >= 0 ? device : 0, d1 = device >= 0 ? device + 1 : nlog;
-  DeviceGuard g;
-  // one device's copy, built in place in s.dev: release() frees whatever a failed step leaves behind
-  auto fill = [&](DeviceCopy& c, int d) -> int {
-    const int phys = s.alias_n > 0 ? 0 : d;
-    c.device = d;
-    c.phys = phys;
-    HIPCHK(hipSetDevice(phys), "hipSetDevice");
-    c.bytes = blob.size();
-    HIPCHK(hipMalloc(&c.block, c.bytes), "hipMalloc(scene)");
-    HIPCHK(hipMemcpy(c.block, blob.data(), c.bytes, hipMemcpyHostToDevice), "hipMemcpy(scene)");
-    HIPCHK(hipMalloc((void**)&c.counters, COUNTER_WORDS * sizeof(unsigned long long)), "hipMalloc(counters)");
-    // the sticky traversal-error word lives in host memory the kernel writes through (coherent,
-    // mapped): the host reads it without a device round trip, also for renders it did not wait for
-    HIPCHK(hipHostMalloc((void**)&c.err_host, 64, hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc(error word)");
-    *(volatile uint32_t*)c.err_host = 0u;
-    uint8_t* base = (uint8_t*)c.block;
-    c.scene.nodes = (const DevNode4*)(base + o_nodes);
-    c.scene.hnodes = f.nodes4h.empty() ? nullptr : (const DevNode4h*)(base + o_hnodes);
-    c.scene.prims = (const DevPrim*)(base + o_prims);
-    c.scene.always = (const uint32_t*)(base + o_always);
-    c.scene.tshade = (const DevTriShade*)(base + o_tsh);
-    c.scene.insts = (const DevInst*)(base + o_inst);
-    c.scene.mats = (const DevMat*)(base + o_mat);
-    c.scene.texs = (const DevTex*)(base + o_tex);
-    c.scene.texels = (const uint8_t*)(base + o_texel);
-    c.scene.perlins = (const DevPerlin*)(base + o_perlin);
-    c.scene.shade = (const DevShade*)(base + o_shade);
-    c.scene.lgroups = (const DevGroup*)(base + o_groups);
-    c.scene.n_lgroups = (uint32_t)f.lgroups.size();
-    c.scene.n_nodes = (uint32_t)f.nodes4.size();
-    c.scene.n_prims = (uint32_t)f.prims.size();
-    c.scene.n_always = (uint32_t)f.always.size();
-    c.scene.n_insts = (uint32_t)f.insts.size();
-    c.scene.msphere_unit = f.msphere_unit;
-    c.scene.uni_inst = f.uni_inst;
-    c.scene.bvh_tri = f.bvh_tri;  // knob RTW_TRI_LEAF (rtw_flatten.cpp)
-    c.scene.tri_inst = f.tri_inst;
-    c.scene.rect_fast = f.rect_fast;
-    memcpy(c.scene.uni_off, f.uni_off, sizeof f.uni_off);
-    c.scene.far_check = f.far_check;
-    return RTW_OK;
-  };
-  for (int d = d0; d < d1; ++d) {
-    s.dev.emplace_back();
-    if (int e = fill(s.dev.back(), d)) {
-      release(s);
-      return e;
-    }
-  }
-  return RTW_OK;
-}
-
-static void free_buf(DevBuf& b) {
-  if (b.p) hipFree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
-}
-
-void release(Scene& s) {
-  for (DeviceCopy& c : s.dev) {
-    if (hipSetDevice(c.phys) != hipSuccess) continue;
-    if (c.block) hipFree(c.block);
-    if (c.counters) hipFree(c.counters);
-    if (c.err_host) hipHostFree(c.err_host);
-    for (DevBuf* b : {&c.sbuf, &c.spill, &c.image, &c.tiles, &c.packed, &c.gathered, &c.gather_ids}) free_buf(*b);
-    for (void* e : c.ev)
-      if (e) hipEventDestroy(static_cast<hipEvent_t>(e));
-    for (void* e : c.gev)
-      if (e) hipEventDestroy(static_cast<hipEvent_t>(e));
-    if (c.stream) hipStreamDestroy(static_cast<hipStream_t>(c.stream));
-    for (auto& e : c.kev)
-      for (void* x : e)
-        if (x) hipEventDestroy(static_cast<hipEvent_t>(x));
-  }
-  s.dev.clear();
-}
-
-DeviceCopy* find_copy(Scene& s, int device) {
-  for (DeviceCopy& c : s.dev)
-    if (c.device == device || device < 0) return &c;
-  return nullptr;
-}
-
-int grow(DevBuf& b, size_t bytes) {
-  if (bytes <= b.cap) return RTW_OK;
-  free_buf(b);
-  HIPCHK(hipMalloc(&b.p, bytes), "hipMalloc(render buffer)");
-  b.cap = bytes;
-  return RTW_OK;
-}
-
-// the scene copy's event pair (created once)
-static int copy_events(DeviceCopy& c, hipEvent_t& e0, hipEvent_t& e1) {
-  for (void*& e : c.ev)
-    if (!e) {
-      hipEvent_t x;
-      HIPCHK(hipEventCreate(&x), "hipEventCreate");
-      e = x;
-    }
-  e0 = static_cast<hipEvent_t>(c.ev[0]);
-  e1 = static_cast<hipEvent_t>(c.ev[1]);
-  return RTW_OK;
-}
-
 // Paths per pass (ordered sample buffer = 12 B per path): 2^32 = 51.5 GB of the 288 GB HBM.  A frame
 // with more paths (monument 4K x 1024 spp: 8.5 G, 2 passes) runs in several passes, each one persistent
 // launch + its in-order reduction.  Tuning knob RTW_PASS_LOG2 (24..33).
@@ -414,9 +268,9 @@ static int resident_grid(DeviceCopy& c, const Variant& var, bool count, bool ver
   const path_fn fn = var.fn[count];
   const int block = var.cfg.blk;
   int& g = c.grid[count ? 1 : 0];
-  void*& gf = c.grid_fn[count ? 1 : 0];
-  if (g > 0 && gf == (void*)fn) return g;
-  gf = (void*)fn;
+  const void*& gf = c.grid_fn[count ? 1 : 0];
+  if (g > 0 && gf == (const void*)fn) return g;
+  gf = (const void*)fn;
   int per_cu = 0, cus = 0;
   hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, block, 0);
   if (e != hipSuccess || per_cu < 1) per_cu = 1;
@@ -427,47 +281,14 @@ static int resident_grid(DeviceCopy& c, const Variant& var, bool count, bool ver
   return g;
 }
 
-// RN(1 / b) for an integer-valued b in [1, 2^24): the float nearest 1 / b, chosen among the neighbours of
-// the double quotient by the exact residual |1 - y b| (y b is exact in double: 24 x 24 bits)
-static float recip_rn(float b) {
-  float y = (float)(1.0 / (double)b), best = y;
-  double e = fabs(1.0 - (double)y * (double)b);
-  for (float c : {nextafterf(y, 0.0f), nextafterf(y, 2.0f)}) {
-    const double ec = fabs(1.0 - (double)c * (double)b);
-    if (ec < e) { e = ec; best = c; }
-  }
-  return best;
-}
-
 // A batch size (knob RTW_BATCH) as the kernels take it: within [64, 65536] and rounded down to a multiple of 64.
 // Passes hold 64 x spp ids per slot, so every batch of a pass, its last one included, is then whole groups of 64
 // consecutive ids: path_kernel's start ring (SRING) builds 64 starts from pool_next + lane without a bound check.
 static uint32_t batch_ids(int v) { return (uint32_t)std::min(65536, std::max(64, v)) & ~63u; }
 
-int check_guard(DeviceCopy& c) {
-  volatile uint32_t* e = c.err_host;
-  if (e && *e) {
-    *e = 0u;
-    return fail(RTW_EINVAL, "a path kernel on device %d tripped its BVH traversal guard (corrupt tree?): the frame "
-                "it rendered is invalid", c.device);
-  }
-  return RTW_OK;
-}
-
-int enqueue_render(Scene& sc, DeviceCopy& c, const rtw_camera* cam, const float bg[3], uint32_t w, uint32_t h,
-                   uint32_t spp, uint32_t max_depth, uint64_t seed, const TileSet& ts, float* d_out, void* stream_,
-                   uint32_t flags, void* ev0_, void* ev1_) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  hipEvent_t ev0 = static_cast<hipEvent_t>(ev0_), ev1 = static_cast<hipEvent_t>(ev1_);
-  const uint32_t* d_tiles = ts.ids;
-  const uint32_t n_slots = ts.n;
-  // an earlier render on this device (one the caller did not wait on) tripped the guard: report it now
-  if (int e = check_guard(c)) return e;
-  if (w > 65536u || h > 65536u)
-    return fail(RTW_EINVAL, "image %ux%u: at most 65536 x 65536 (16-bit pixel coordinates in the path key)", w, h);
-  if (cam->time0 < sc.flat.time_lo || cam->time1 > sc.flat.time_hi)
-    return fail(RTW_EINVAL, "camera shutter [%g, %g) outside the committed motion range [%g, %g]",
-                cam->time0, cam->time1, sc.flat.time_lo, sc.flat.time_hi);
+// enqueue_render, part 1: the RenderArgs of a frame and its tiles, all but the launch tuning.  Pure host arithmetic.
+static RenderArgs frame_args(const DeviceCopy& c, const Frame& f, const TileSet& ts, float* d_out) {
+  const rtw_camera* cam = f.cam;
   RenderArgs a;
   memset(&a, 0, sizeof a);
   a.scene = c.scene;
@@ -480,12 +301,12 @@ int enqueue_render(Scene& sc, DeviceCopy& c, const rtw_camera* cam, const float 
   a.cam.lens_radius = cam->lens_radius;
   a.cam.time0 = cam->time0;
   a.cam.time1 = cam->time1;
-  memcpy(a.bg, bg, sizeof a.bg);
-  a.w = w; a.h = h; a.spp = spp; a.max_depth = max_depth;
-  a.tiles_x = (w + 7u) / 8u;
-  a.spp_magic = spp > 1u ? UINT64_MAX / spp + 1u : 0u;
-  a.fw1 = (float)(w - 1u);
-  a.fh1 = (float)(h - 1u);
+  memcpy(a.bg, f.bg, sizeof a.bg);
+  a.w = f.w; a.h = f.h; a.spp = f.spp; a.max_depth = f.max_depth;
+  a.tiles_x = f.tiles_x();
+  a.spp_magic = f.spp > 1u ? UINT64_MAX / f.spp + 1u : 0u;
+  a.fw1 = (float)(f.w - 1u);
+  a.fh1 = (float)(f.h - 1u);
   a.rw1 = recip_rn(a.fw1);
   a.rh1 = recip_rn(a.fh1);
   {
@@ -493,136 +314,153 @@ int enqueue_render(Scene& sc, DeviceCopy& c, const rtw_camera* cam, const float 
     a.time_span = t1 - t0;
   }
   a.tiles_x_magic = a.tiles_x > 1u ? UINT64_MAX / a.tiles_x + 1u : 0u;
-  a.tile_ids = d_tiles;
+  a.tile_ids = ts.ids;
   a.tile_first = ts.first;
   a.tile_stride = ts.stride;
-  a.packed_out = (d_tiles || ts.packed) ? 1u : 0u;
+  a.packed_out = (ts.ids || ts.packed) ? 1u : 0u;
   a.err = c.err_host;
-  const Knobs kn = read_knobs();
-  // see trace_run (measured best of 4..16 on jumpy-balls); tuning knob RTW_QUOTA16 (1..16)
-  a.quota16 = (uint32_t)std::min(16, std::max(1, kn.quota16.get(12)));
   // the host mirror of dev::splitmix64 (seed pre-hash shared by every pixel)
-  uint64_t z = seed + 0x9E3779B97F4A7C15ull;
+  uint64_t z = f.seed + 0x9E3779B97F4A7C15ull;
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   a.seed_hash = z ^ (z >> 31);
   a.out = d_out;
   a.counters = c.counters;
   a.queue = c.counters + 32;  // the DISP path-id dispensers (path_kernel), DISP_STRIDE words apart
+  return a;
+}
+
+// enqueue_render, part 2: the launch tuning of variant k on `grid` resident workgroups, into a.  a.batch is the
+// full-frame value: pass_batch shrinks it for a small pass.
+static void tune_launch(RenderArgs& a, const Knobs& kn, const Flat& flat, const KernelCfg& k, int grid) {
+  // see trace_run (measured best of 4..16 on jumpy-balls); tuning knob RTW_QUOTA16 (1..16)
+  a.quota16 = (uint32_t)std::min(16, std::max(1, kn.quota16.get(12)));
+  // test postponed leaves once leaf16/16 of the wave's lanes hold one and cannot descend (trace_run); knob
+  // RTW_LEAF16 (1..16).  The sorted-push walk of the LDS-node kernels parks fewer leaves early: 5/16 measured best
+  // on jumpy-balls (+0.5% over 3; profiles/r02/experiments, n5)
+  const bool ldsn_spheres = k.lds_nodes() && flat.features == (flat.features & F_SPHERES);
+  a.leaf16 = (uint32_t)std::min(16, std::max(1, kn.leaf16.get(ldsn_spheres ? 5 : 3)));
+  // whole wave-loads of ids only (batch_ids): the start ring makes 64 path starts from 64 consecutive ids of a batch.
+  // The 1024-lane LDS-node kernel and the BVH-less list kernels: 1024 ids per atomic (a shorter end-of-frame
+  // tail; jumpy-1080p +1.2%, cornell-800 +0.5% over 2048, profiles/r03/experiments k3 / k4); the mesh
+  // kernels keep 2048 (neutral on cow; their short paths made small batches costly in round 2)
+  const bool small_batch = (k.lds_nodes() && k.blk == 1024) || flat.nodes4.empty();
+  a.batch = batch_ids(kn.batch.get(small_batch ? 1024 : (int)dev::BATCH));
+  // Regenerate paths only once >= regen_min lanes of a wave are idle (or all are): start_path
+  // runs at wave level, so batching it raises its SIMD utilisation.  Measured on MI355X
+  // (RTW_REGEN_MIN sweep 1..32): 24 is best for open scenes (jumpy-balls +4.3%, cow +1.6%,
+  // monument +1.7% over 1); closed boxes (cornell: 6.6 segments per path, few lanes finish per
+  // iteration) lose with deep deferral: 8 (cornell list variant at 8 waves/SIMD: 29.3k at 1, 29.4k at 4, 29.8k at 8, 28.1k at 24).
+  // With the start ring (round 6, the rect list kernel) a regeneration costs a few LDS reads, not start_path at
+  // the idle lanes' occupancy, so waves refill early: REGEN_RING (cornell-800: 8 -> 2, +1.8%).  The 1024-lane
+  // sphere kernel's take finishes the start (start_take) and its paths are shorter: REGEN_RING_LDSN
+  // (profiles/r07/experiments).
+  const bool boxed = (flat.features & ~F_SMOKE) == 0;
+  const int regen_dflt = k.ldsn_ring() ? REGEN_RING_LDSN : (k.sring() ? REGEN_RING : (boxed ? 8 : 24));
+  a.regen_min = (uint32_t)std::min(64, std::max(1, kn.regen_min.get(regen_dflt)));
+  // the LDS-node variants walk 16-bit codes within their own stack rows (pick_kernel checked
+  // stack_need4 against them) and have no HBM spill path
+  const uint32_t lds = (uint32_t)k.stack;
+  a.spill_depth = (!k.lds_nodes() && flat.stack_need > lds) ? flat.stack_need - lds : 0;
+  a.spill_lanes = (uint32_t)grid * (uint32_t)k.blk;
+}
+
+// Small frames: fewer ids per atomic, halving until every resident wave can take >= 32 batches.  configs[0]
+// (jumpy-balls 400x225x50: 4.5 M paths for 8,192 resident waves) handed out 4,395 batches of 1,024, so half the
+// waves got none and the kernel ran 5x slower per ray than at 1080p: 5.43k -> 9.30k Mrays/s at 128.  The same
+// for an 8-GPU share (one eighth of the paths): jumpy +5% at 256, cornell +4.4% at 256, cow +22% at 512
+// (profiles/r05/experiments, r05l).  Floors: the mesh / generic kernels' short paths queue on the one atomic
+// word below 512 (cow 256: -16%), the others' below 128.  Full frames keep the defaults (>= 32 batches per
+// wave already); knob RTW_BATCH sets the size outright.
+// (a pass this rule gave smaller batches spreads its atomics over DISP words in the LDS-node kernels:
+// path_kernel SHARD; r06 share8: an 8-GPU share of jumpy-1080p +5%, configs[0] +11%)
+static uint32_t pass_batch(uint32_t batch0, uint64_t n_paths, uint64_t waves) {
+  const uint32_t batch_floor = batch0 >= 2048u ? 512u : 128u;
+  uint32_t batch = batch0;
+  while (batch / 2u >= batch_floor && n_paths < (uint64_t)batch * waves * 32u) batch /= 2u;
+  return batch;
+}
+
+// enqueue_render, part 3: the pass loop over n_slots tiles, each pass one persistent launch of the scene's variant and
+// its in-order reduction
+static int run_passes(Scene& sc, DeviceCopy& c, RenderArgs& a, const Knobs& kn, uint32_t n_slots, bool count,
+                      hipStream_t stream) {
+  const uint64_t per_slot = 64ull * a.spp;
+  const uint32_t slots_per_pass = (uint32_t)std::max<uint64_t>(1, max_pass_paths(kn) / per_slot);
+  const uint64_t need = std::min<uint64_t>(n_slots, slots_per_pass) * per_slot;
+  if (int e = grow(c.sbuf, need * 3 * sizeof(float))) return e;  // the ordered sample buffer (first render only)
+  a.sbuf = static_cast<float*>(c.sbuf.p);
+  const Variant var = path_kernel_variant(sc.flat, kn);
+  const KernelCfg& k = var.cfg;
+  const int grid = resident_grid(c, var, count, kn.verbose);
+  tune_launch(a, kn, sc.flat, k, grid);
+  // (first render of a deep tree only)
+  if (int e = grow(c.spill, (size_t)a.spill_depth * a.spill_lanes * sizeof(int32_t))) return e;
+  a.spill = static_cast<int32_t*>(c.spill.p);
+  const uint32_t batch0 = a.batch;
+  const uint64_t waves = (uint64_t)grid * (uint32_t)k.blk / 64u;
+  for (uint32_t base = 0; base < n_slots; base += slots_per_pass) {
+    const uint32_t ns = std::min(slots_per_pass, n_slots - base);
+    a.slot_base = base;
+    a.n_paths = (uint64_t)ns * per_slot;
+    a.batch = kn.batch.set ? batch0 : pass_batch(batch0, a.n_paths, waves);
+    if (base) HIPCHK(hipMemsetAsync(a.queue, 0, DISP * DISP_STRIDE * sizeof(unsigned long long), stream),
+                     "hipMemsetAsync(queue)");
+    hipEvent_t* ke = c.kev[c.kev_head];
+    if (int e = ensure_event(ke[0])) return e;
+    if (int e = ensure_event(ke[1])) return e;
+    HIPCHK(hipEventRecord(ke[0], stream), "hipEventRecord");
+    hipLaunchKernelGGL(var.fn[count], dim3(grid), dim3(k.blk), 0, stream, a);
+    HIPCHK(hipGetLastError(), "path_kernel launch");
+    HIPCHK(hipEventRecord(ke[1], stream), "hipEventRecord");
+    c.kev_head = (c.kev_head + 1) % 64u;
+    c.kev_count = std::min(c.kev_count + 1u, 64u);
+    hipLaunchKernelGGL(dev::reduce_kernel, dim3((ns * 64u + 255u) / 256u), dim3(256), 0, stream, a, ns);
+    HIPCHK(hipGetLastError(), "reduce_kernel launch");
+  }
+  return RTW_OK;
+}
+
+int enqueue_render(Scene& sc, DeviceCopy& c, const Frame& f, const TileSet& ts, float* d_out, hipStream_t stream,
+                   uint32_t flags, hipEvent_t ev0, hipEvent_t ev1) {
+  // an earlier render on this device (one the caller did not wait on) tripped the guard: report it now
+  if (int e = check_guard(c)) return e;
+  if (f.w > 65536u || f.h > 65536u)
+    return fail(RTW_EINVAL, "image %ux%u: at most 65536 x 65536 (16-bit pixel coordinates in the path key)", f.w, f.h);
+  if (f.cam->time0 < sc.flat.time_lo || f.cam->time1 > sc.flat.time_hi)
+    return fail(RTW_EINVAL, "camera shutter [%g, %g) outside the committed motion range [%g, %g]",
+                f.cam->time0, f.cam->time1, sc.flat.time_lo, sc.flat.time_hi);
+  RenderArgs a = frame_args(c, f, ts, d_out);
+  const Knobs kn = read_knobs();
   HIPCHK(hipMemsetAsync(c.counters, 0, COUNTER_WORDS * sizeof(unsigned long long), stream), "hipMemsetAsync");
   if (ev0) HIPCHK(hipEventRecord(ev0, stream), "hipEventRecord");
-  if (n_slots && (spp == 0 || max_depth == 0)) {  // lib.rs:83 loops 0 times / :98 returns black
-    size_t n = a.packed_out ? (size_t)n_slots * 64 * 3 : (size_t)w * h * 3;
+  if (ts.n && (f.spp == 0 || f.max_depth == 0)) {  // lib.rs:83 loops 0 times / :98 returns black
+    size_t n = a.packed_out ? (size_t)ts.n * 64 * 3 : (size_t)f.w * f.h * 3;
     HIPCHK(hipMemsetAsync(d_out, 0, n * sizeof(float), stream), "hipMemsetAsync(out)");
-  } else if (n_slots) {
-    const uint64_t per_slot = 64ull * spp;
-    const uint32_t slots_per_pass = (uint32_t)std::max<uint64_t>(1, max_pass_paths(kn) / per_slot);
-    const uint64_t need = std::min<uint64_t>(n_slots, slots_per_pass) * per_slot;
-    if (int e = grow(c.sbuf, need * 3 * sizeof(float))) return e;  // the ordered sample buffer (first render only)
-    a.sbuf = static_cast<float*>(c.sbuf.p);
-    const bool count = flags & RTW_FLAG_COUNT_TRAVERSAL;
-    const Variant var = path_kernel_variant(sc.flat, kn);
-    const KernelCfg& k = var.cfg;
-    // test postponed leaves once leaf16/16 of the wave's lanes hold one and cannot descend (trace_run); knob
-    // RTW_LEAF16 (1..16).  The sorted-push walk of the LDS-node kernels parks fewer leaves early: 5/16 measured best
-    // on jumpy-balls (+0.5% over 3; profiles/r02/experiments, n5)
-    const bool ldsn_spheres = k.lds_nodes() && sc.flat.features == (sc.flat.features & F_SPHERES);
-    a.leaf16 = (uint32_t)std::min(16, std::max(1, kn.leaf16.get(ldsn_spheres ? 5 : 3)));
-    // whole wave-loads of ids only (batch_ids): the start ring makes 64 path starts from 64 consecutive ids of a batch.
-    // The 1024-lane LDS-node kernel and the BVH-less list kernels: 1024 ids per atomic (a shorter end-of-frame
-    // tail; jumpy-1080p +1.2%, cornell-800 +0.5% over 2048, profiles/r03/experiments k3 / k4); the mesh
-    // kernels keep 2048 (neutral on cow; their short paths made small batches costly in round 2)
-    const bool small_batch = (k.lds_nodes() && k.blk == 1024) || sc.flat.nodes4.empty();
-    a.batch = batch_ids(kn.batch.get(small_batch ? 1024 : (int)dev::BATCH));
-    // Regenerate paths only once >= regen_min lanes of a wave are idle (or all are): start_path
-    // runs at wave level, so batching it raises its SIMD utilisation.  Measured on MI355X
-    // (RTW_REGEN_MIN sweep 1..32): 24 is best for open scenes (jumpy-balls +4.3%, cow +1.6%,
-    // monument +1.7% over 1); closed boxes (cornell: 6.6 segments per path, few lanes finish per
-    // iteration) lose with deep deferral: 8 (cornell list variant at 8 waves/SIMD: 29.3k at 1, 29.4k at 4, 29.8k at 8, 28.1k at 24).
-    // With the start ring (round 6, the rect list kernel) a regeneration costs a few LDS reads, not start_path at
-    // the idle lanes' occupancy, so waves refill early: REGEN_RING (cornell-800: 8 -> 2, +1.8%).  The 1024-lane
-    // sphere kernel's take finishes the start (start_take) and its paths are shorter: REGEN_RING_LDSN
-    // (profiles/r07/experiments).
-    const bool boxed = (sc.flat.features & ~F_SMOKE) == 0;
-    const int regen_dflt = k.ldsn_ring() ? REGEN_RING_LDSN : (k.sring() ? REGEN_RING : (boxed ? 8 : 24));
-    a.regen_min = (uint32_t)std::min(64, std::max(1, kn.regen_min.get(regen_dflt)));
-    const int grid = resident_grid(c, var, count, kn.verbose);
-    // Small frames: fewer ids per atomic, halving until every resident wave can take >= 32 batches.  configs[0]
-    // (jumpy-balls 400x225x50: 4.5 M paths for 8,192 resident waves) handed out 4,395 batches of 1,024, so half the
-    // waves got none and the kernel ran 5x slower per ray than at 1080p: 5.43k -> 9.30k Mrays/s at 128.  The same
-    // for an 8-GPU share (one eighth of the paths): jumpy +5% at 256, cornell +4.4% at 256, cow +22% at 512
-    // (profiles/r05/experiments, r05l).  Floors: the mesh / generic kernels' short paths queue on the one atomic
-    // word below 512 (cow 256: -16%), the others' below 128.  Full frames keep the defaults (>= 32 batches per
-    // wave already); knob RTW_BATCH sets the size outright.
-    const uint32_t batch0 = a.batch, batch_floor = batch0 >= 2048u ? 512u : 128u;
-    const bool batch_auto = !kn.batch.set;
-    const uint64_t waves = (uint64_t)grid * (uint32_t)k.blk / 64u;
-    // the LDS-node variants walk 16-bit codes within their own stack rows (pick_kernel checked
-    // stack_need4 against them) and have no HBM spill path
-    const uint32_t lds = (uint32_t)k.stack;
-    a.spill_depth = (!k.lds_nodes() && sc.flat.stack_need > lds) ? sc.flat.stack_need - lds : 0;
-    a.spill_lanes = (uint32_t)grid * (uint32_t)k.blk;
-    // (first render of a deep tree only)
-    if (int e = grow(c.spill, (size_t)a.spill_depth * a.spill_lanes * sizeof(int32_t))) return e;
-    a.spill = static_cast<int32_t*>(c.spill.p);
-    for (uint32_t base = 0; base < n_slots; base += slots_per_pass) {
-      const uint32_t ns = std::min(slots_per_pass, n_slots - base);
-      a.slot_base = base;
-      a.n_paths = (uint64_t)ns * per_slot;
-      a.batch = batch0;
-      if (batch_auto)
-        while (a.batch / 2u >= batch_floor && a.n_paths < (uint64_t)a.batch * waves * 32u) a.batch /= 2u;
-      // (a pass the rule above gave smaller batches spreads its atomics over DISP words in the LDS-node kernels:
-      // path_kernel SHARD; r06 share8: an 8-GPU share of jumpy-1080p +5%, configs[0] +11%)
-      if (base) HIPCHK(hipMemsetAsync(a.queue, 0, DISP * DISP_STRIDE * sizeof(unsigned long long), stream),
-                       "hipMemsetAsync(queue)");
-      hipEvent_t* ke = reinterpret_cast<hipEvent_t*>(c.kev[c.kev_head]);
-      if (!ke[0]) HIPCHK(hipEventCreate(&ke[0]), "hipEventCreate");
-      if (!ke[1]) HIPCHK(hipEventCreate(&ke[1]), "hipEventCreate");
-      HIPCHK(hipEventRecord(ke[0], stream), "hipEventRecord");
-      hipLaunchKernelGGL(var.fn[count], dim3(grid), dim3(k.blk), 0, stream, a);
-      HIPCHK(hipGetLastError(), "path_kernel launch");
-      HIPCHK(hipEventRecord(ke[1], stream), "hipEventRecord");
-      c.kev_head = (c.kev_head + 1) % 64u;
-      c.kev_count = std::min(c.kev_count + 1u, 64u);
-      hipLaunchKernelGGL(dev::reduce_kernel, dim3((ns * 64u + 255u) / 256u), dim3(256), 0, stream, a, ns);
-      HIPCHK(hipGetLastError(), "reduce_kernel launch");
-    }
+  } else if (ts.n) {
+    if (int e = run_passes(sc, c, a, kn, ts.n, flags & RTW_FLAG_COUNT_TRAVERSAL, stream)) return e;
   }
   if (ev1) HIPCHK(hipEventRecord(ev1, stream), "hipEventRecord");
   return RTW_OK;
 }
 
-int collect_stats(DeviceCopy& c, void* stream_, void* ev0_, void* ev1_, uint64_t paths, rtw_stats* st) {
-  hipEvent_t ev0 = static_cast<hipEvent_t>(ev0_), ev1 = static_cast<hipEvent_t>(ev1_);
-  HIPCHK(hipStreamSynchronize(static_cast<hipStream_t>(stream_)), "render_kernel");
-  unsigned long long cnt[32];
-  HIPCHK(hipMemcpy(cnt, c.counters, sizeof cnt, hipMemcpyDeviceToHost), "hipMemcpy(counters)");
-  float ms = 0.f;
-  if (ev0 && ev1) HIPCHK(hipEventElapsedTime(&ms, ev0, ev1), "hipEventElapsedTime");
-  if (int e = check_guard(c)) return e;
-  st->rays = cnt[0];
-  st->paths = paths;
-  st->kernel_ms = ms;
-  st->node_visits = cnt[1];
-  st->prim_tests = cnt[2];
-  for (int k = 0; k < 6; ++k) st->prim_tests_by_type[k] = cnt[3 + k];
-  for (int k = 0; k < 6; ++k) st->simd[k] = cnt[9 + k];
-  for (int k = 0; k < 4; ++k) st->phase_cycles[k] = cnt[16 + k];
-  st->boxes_tested = cnt[15];
-  for (int k = 0; k < 4; ++k) st->sub_cycles[k] = cnt[20 + k];
-  return RTW_OK;
-}
-
 int enqueue_unpack(uint32_t w, uint32_t h, const uint32_t* d_tiles, uint32_t n_tiles, const float* d_packed,
-                   float* d_image, void* stream) {
+                   float* d_image, hipStream_t stream) {
   const uint32_t n = n_tiles * 64u;
   if (!n) return RTW_OK;
-  hipLaunchKernelGGL(dev::unpack_tiles_kernel, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     w, h, (w + 7u) / 8u, d_tiles, n_tiles, d_packed, d_image);
+  hipLaunchKernelGGL(dev::unpack_tiles_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, w, h, (w + 7u) / 8u, d_tiles,
+                     n_tiles, d_packed, d_image);
   HIPCHK(hipGetLastError(), "unpack_tiles_kernel");
   return RTW_OK;
 }
+
+// a diagnostic call's device array of n Ts, freed on every return path
+template <class T>
+struct DiagBuf {
+  T* p = nullptr;
+  bool alloc(size_t n) { return hipMalloc((void**)&p, n * sizeof(T)) == hipSuccess; }
+  ~DiagBuf() { hipFree(p); }
+};
 
 }  // namespace rtw
 
@@ -630,285 +468,39 @@ using namespace rtw;
 
 extern "C" {
 
-int rtw_device_count(void) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-  return n;
-}
-
-int rtw_render(rtw_scene* s, const rtw_camera* cam, const float bg[3], uint32_t w, uint32_t h,
-               uint32_t spp, uint32_t max_depth, uint64_t seed, float* out, rtw_stats* stats) {
-  auto t0 = std::chrono::steady_clock::now();
-  if (!s || !cam || !bg || !out) return fail(RTW_EINVAL, "NULL argument");
-  if (!s->s.committed) return fail(RTW_ESTATE, "scene not committed");
-  if (w < 2 || h < 2) return fail(RTW_EINVAL, "image must be at least 2x2 (lib.rs:84-85 divides by w-1, h-1)");
-  DeviceCopy* c = find_copy(s->s, -1);
-  if (!c) return fail(RTW_ENODEV, "scene has no device copy");
-  DeviceGuard g;
-  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
-  const size_t bytes = (size_t)w * h * 3 * sizeof(float);
-  hipEvent_t e0, e1;
-  if (int e = copy_events(*c, e0, e1)) return e;
-  if (int e = grow(c->image, bytes)) return e;  // kept for the next frame (no per-call hipMalloc)
-  float* d_out = static_cast<float*>(c->image.p);
-  const uint32_t n_tiles = ((w + 7u) / 8u) * ((h + 7u) / 8u);
-  rtw_stats st;
-  memset(&st, 0, sizeof st);
-  TileSet all;
-  all.n = n_tiles;
-  int rc = enqueue_render(s->s, *c, cam, bg, w, h, spp, max_depth, seed, all, d_out, nullptr, 0, e0, e1);
-  if (rc == RTW_OK) rc = collect_stats(*c, nullptr, e0, e1, (uint64_t)w * h * spp, &st);
-  if (rc == RTW_OK && hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost) != hipSuccess)
-    rc = fail(RTW_ENODEV, "hipMemcpy(image)");
-  st.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  if (stats) *stats = st;
-  return rc;
-}
-
-static int render_device(rtw_scene* s, int device, const rtw_camera* cam, const float bg[3], uint32_t w, uint32_t h,
-                         uint32_t spp, uint32_t max_depth, uint64_t seed, TileSet ts, float* d_out, void* stream,
-                         uint32_t flags, rtw_stats* stats) {
-  auto t0 = std::chrono::steady_clock::now();
-  if (!s || !cam || !bg || !d_out) return fail(RTW_EINVAL, "NULL argument");
-  if (!s->s.committed) return fail(RTW_ESTATE, "scene not committed");
-  if (w < 2 || h < 2) return fail(RTW_EINVAL, "image must be at least 2x2");
-  DeviceCopy* c = find_copy(s->s, device);
-  if (!c) return fail(RTW_ENODEV, "scene was not committed to device %d", device);
-  DeviceGuard g;
-  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (stats)
-    if (int e = copy_events(*c, e0, e1)) return e;
-  int rc = enqueue_render(s->s, *c, cam, bg, w, h, spp, max_depth, seed, ts, d_out, stream, flags, e0, e1);
-  if (rc == RTW_OK && stats) {
-    rtw_stats st;
-    memset(&st, 0, sizeof st);
-    rc = collect_stats(*c, stream, e0, e1, (uint64_t)ts.n * 64u * spp, &st);
-    st.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    *stats = st;
-  }
-  return rc;
-}
-
-int rtw_render_device(rtw_scene* s, int device, const rtw_camera* cam, const float bg[3], uint32_t w,
-                      uint32_t h, uint32_t spp, uint32_t max_depth, uint64_t seed, const uint32_t* d_tiles,
-                      uint32_t n_tiles, float* d_out, void* stream, uint32_t flags, rtw_stats* stats) {
-  TileSet ts;
-  ts.ids = d_tiles;
-  ts.n = d_tiles ? n_tiles : ((w + 7u) / 8u) * ((h + 7u) / 8u);
-  return render_device(s, device, cam, bg, w, h, spp, max_depth, seed, ts, d_out, stream, flags, stats);
-}
-
-int rtw_render_device_strided(rtw_scene* s, int device, const rtw_camera* cam, const float bg[3], uint32_t w,
-                              uint32_t h, uint32_t spp, uint32_t max_depth, uint64_t seed, uint32_t first_tile,
-                              uint32_t tile_stride, uint32_t n_tiles, float* d_out, void* stream, uint32_t flags,
-                              rtw_stats* stats) {
-  const uint64_t nt = (uint64_t)((w + 7u) / 8u) * ((h + 7u) / 8u);
-  if (tile_stride == 0 || (n_tiles && first_tile + (uint64_t)(n_tiles - 1) * tile_stride >= nt))
-    return fail(RTW_EINVAL, "tiles %u + k * %u (k < %u) leave the frame's %llu tiles", first_tile, tile_stride, n_tiles,
-                (unsigned long long)nt);
-  TileSet ts;
-  ts.first = first_tile;
-  ts.stride = tile_stride;
-  ts.n = n_tiles;
-  ts.packed = true;
-  return render_device(s, device, cam, bg, w, h, spp, max_depth, seed, ts, d_out, stream, flags, stats);
-}
-
-int rtw_render_status(rtw_scene* s, int device) {
-  if (!s) return fail(RTW_EINVAL, "NULL argument");
-  DeviceCopy* c = find_copy(s->s, device);
-  if (!c) return fail(RTW_ENODEV, "scene was not committed to device %d", device);
-  DeviceGuard g;
-  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
-  HIPCHK(hipDeviceSynchronize(), "render (hipDeviceSynchronize)");
-  return check_guard(*c);
-}
-
-// Test hook: overwrite the first two node4s of the device copy with a cycle (node 0 -> node 1 -> node 1
-// ..., every box infinite, in both the 32-bit child words and the 16-bit codes), so that every ray's
-// walk trips the traversal guard.  The host tables are untouched; renders of this copy are invalid.
-int rtw_diag_corrupt_bvh(rtw_scene* s, int device) {
-  if (!s) return fail(RTW_EINVAL, "NULL argument");
-  if (!s->s.committed) return fail(RTW_ESTATE, "scene not committed");
-  DeviceCopy* c = find_copy(s->s, device);
-  if (!c) return fail(RTW_ENODEV, "scene was not committed to device %d", device);
-  if (c->scene.n_nodes < 2) return fail(RTW_EINVAL, "the scene's BVH has %u node4s (needs 2)", c->scene.n_nodes);
-  DevNode4 nd[2];
-  memset(nd, 0, sizeof nd);
-  for (DevNode4& n : nd) {
-    for (int k = 0; k < 4; ++k) {
-      const float lo = k ? INFINITY : -1e30f, hi = k ? -INFINITY : 1e30f;  // slots 1-3 empty
-      n.lo_x[k] = n.lo_y[k] = n.lo_z[k] = lo;
-      n.hi_x[k] = n.hi_y[k] = n.hi_z[k] = hi;
-    }
-    n.child[0] = 1;
-    n.code[0] = 1u;
-  }
-  DeviceGuard g;
-  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
-  HIPCHK(hipMemcpy(const_cast<DevNode4*>(c->scene.nodes), nd, sizeof nd, hipMemcpyHostToDevice), "hipMemcpy(nodes)");
-  if (c->scene.hnodes) {  // the half-precision table too: slot 0 = [-65504, +inf) on every axis, slots 1-3 empty
-    DevNode4h hn[2];
-    memset(hn, 0, sizeof hn);
-    for (DevNode4h& n : hn) {
-      for (uint16_t* ax : {&n.x[0][0], &n.y[0][0], &n.z[0][0]})
-        for (int k = 0; k < 4; ++k) {
-          const uint16_t lo = k ? 0x7C00 : 0x0000, hi = k ? 0xFC00 : 0x7C00;
-          ax[k] = lo; ax[4 + k] = hi; ax[8 + k] = hi; ax[12 + k] = lo;
-        }
-      n.origin[0] = n.origin[1] = n.origin[2] = 0xFBFF;  // -65504
-      n.code[0] = 1;
-    }
-    HIPCHK(hipMemcpy(const_cast<DevNode4h*>(c->scene.hnodes), hn, sizeof hn, hipMemcpyHostToDevice), "hipMemcpy(hnodes)");
-  }
-  return RTW_OK;
-}
-
-int rtw_render_stream(rtw_scene* s, const rtw_camera* cam, const float bg[3], uint32_t w, uint32_t h, uint32_t spp,
-                      uint32_t max_depth, uint64_t seed, uint32_t band_rows, rtw_pixel_sink sink, void* user,
-                      rtw_stats* stats) {
-  auto t0 = std::chrono::steady_clock::now();
-  if (!s || !cam || !bg || !sink) return fail(RTW_EINVAL, "NULL argument");
-  if (!s->s.committed) return fail(RTW_ESTATE, "scene not committed");
-  if (w < 2 || h < 2) return fail(RTW_EINVAL, "image must be at least 2x2 (lib.rs:84-85 divides by w-1, h-1)");
-  DeviceCopy* c = find_copy(s->s, -1);
-  if (!c) return fail(RTW_ENODEV, "scene has no device copy");
-  const uint32_t tiles_x = (w + 7u) / 8u, tiles_y = (h + 7u) / 8u;
-  const uint32_t band_ty = std::max(1u, ((band_rows ? band_rows : 64u) + 7u) / 8u);  // tile rows per band
-  DeviceGuard g;
-  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
-  const size_t band_tiles = (size_t)band_ty * tiles_x;
-  if (int e = grow(c->packed, band_tiles * 64 * 3 * sizeof(float))) return e;
-  float* d_packed = static_cast<float*>(c->packed.p);
-  hipEvent_t e0, e1;
-  if (int e = copy_events(*c, e0, e1)) return e;
-  int rc = RTW_OK;
-  std::vector<float> packed(band_tiles * 64 * 3);
-  std::vector<rtw_pixel> px;
-  rtw_stats tot;
-  memset(&tot, 0, sizeof tot);
-  for (uint32_t ty0 = 0; rc == RTW_OK && ty0 < tiles_y; ty0 += band_ty) {
-    const uint32_t nty = std::min(band_ty, tiles_y - ty0), nt = nty * tiles_x;
-    TileSet band;  // tile row ty = output rows [8 ty, 8 ty + 8): the band's tiles are consecutive
-    band.first = ty0 * tiles_x;
-    band.n = nt;
-    band.packed = true;
-    rc = enqueue_render(s->s, *c, cam, bg, w, h, spp, max_depth, seed, band, d_packed, nullptr, 0, e0, e1);
-    rtw_stats st;
-    memset(&st, 0, sizeof st);
-    if (rc == RTW_OK) rc = collect_stats(*c, nullptr, e0, e1, 0, &st);
-    if (rc == RTW_OK && hipMemcpy(packed.data(), d_packed, (size_t)nt * 64 * 3 * sizeof(float),
-                                  hipMemcpyDeviceToHost) != hipSuccess)
-      rc = fail(RTW_ENODEV, "hipMemcpy(band)");
-    if (rc != RTW_OK) break;
-    tot.rays += st.rays;
-    tot.kernel_ms += st.kernel_ms;
-    // emit rows of this band in reference order: output row r <-> j = h-1-r, columns 0..w-1
-    const uint32_t r0 = ty0 * 8u, r1 = std::min(h, (ty0 + nty) * 8u);
-    px.clear();
-    for (uint32_t r = r0; r < r1; ++r)
-      for (uint32_t i = 0; i < w; ++i) {
-        const size_t slot = (size_t)(r / 8u - ty0) * tiles_x + i / 8u, lane = (r % 8u) * 8u + (i % 8u);
-        const float* v = &packed[(slot * 64 + lane) * 3];
-        px.push_back(rtw_pixel{h - 1u - r, i, {v[0], v[1], v[2]}});
-      }
-    if (int e = sink(px.data(), (uint32_t)px.size(), user)) rc = e;
-  }
-  tot.paths = (uint64_t)w * h * spp;
-  tot.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  if (stats) *stats = tot;
-  return rc;
-}
-
-int rtw_path_kernel_times(rtw_scene* s, int device, float* ms, uint32_t max_n) {
-  if (!s || (!ms && max_n)) return fail(RTW_EINVAL, "NULL argument");
-  DeviceCopy* c = find_copy(s->s, device);
-  if (!c) return fail(RTW_ENODEV, "scene was not committed to device %d", device);
-  DeviceGuard g;
-  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
-  const uint32_t n = std::min(c->kev_count, max_n);
-  int rc = (int)n;
-  for (uint32_t q = 0; q < n; ++q) {  // the n most recent, oldest first
-    hipEvent_t* e = reinterpret_cast<hipEvent_t*>(c->kev[(c->kev_head + 64u - n + q) % 64u]);
-    hipError_t err = hipEventSynchronize(e[1]);
-    if (err == hipSuccess) err = hipEventElapsedTime(&ms[q], e[0], e[1]);
-    if (err != hipSuccess) {
-      rc = hip_fail(err, "path-kernel events");
-      break;
-    }
-  }
-  c->kev_count = 0;
-  if (rc >= 0 && n)  // the launches waited for: report a tripped traversal guard (its frame is invalid)
-    if (int e = check_guard(*c)) rc = e;
-  return rc;
-}
-
-int rtw_diag_recip(uint32_t n, const float* b, float* out) {
-  if (n && (!b || !out)) return fail(RTW_EINVAL, "NULL argument");
-  for (uint32_t k = 0; k < n; ++k) out[k] = recip_rn(b[k]);
-  return RTW_OK;
-}
-
 int rtw_diag_libm(int fn, uint32_t n, const float* a, const float* b, float* out) {
   if (fn < 0 || fn > 5 || (n && (!a || !out || ((fn == 3 || fn == 4) && !b)))) return fail(RTW_EINVAL, "bad arguments");
   if (!n) return RTW_OK;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(RTW_ENODEV, "no HIP device visible");
-  float *da = nullptr, *db = nullptr, *dout = nullptr;
+  DiagBuf<float> da, db, dout;
   const size_t bytes = (size_t)n * sizeof(float);
-  int rc = RTW_OK;
-  if (hipMalloc((void**)&da, bytes) != hipSuccess || hipMalloc((void**)&dout, bytes) != hipSuccess ||
-      ((fn == 3 || fn == 4) && hipMalloc((void**)&db, bytes) != hipSuccess)) {
-    rc = fail(RTW_ENOMEM, "hipMalloc(diag)");
-  } else if (hipMemcpy(da, a, bytes, hipMemcpyHostToDevice) != hipSuccess ||
-             (db && hipMemcpy(db, b, bytes, hipMemcpyHostToDevice) != hipSuccess)) {
-    rc = fail(RTW_ENODEV, "hipMemcpy(diag)");
-  } else {
-    hipLaunchKernelGGL(dev::libm_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, fn, n, da, db, dout);
-    if (hipGetLastError() != hipSuccess || hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost) != hipSuccess)
-      rc = fail(RTW_ENODEV, "libm_kernel");
-  }
-  if (da) hipFree(da);
-  if (db) hipFree(db);
-  if (dout) hipFree(dout);
-  return rc;
+  if (!da.alloc(n) || !dout.alloc(n) || ((fn == 3 || fn == 4) && !db.alloc(n))) return fail(RTW_ENOMEM, "hipMalloc(diag)");
+  if (hipMemcpy(da.p, a, bytes, hipMemcpyHostToDevice) != hipSuccess ||
+      (db.p && hipMemcpy(db.p, b, bytes, hipMemcpyHostToDevice) != hipSuccess))
+    return fail(RTW_ENODEV, "hipMemcpy(diag)");
+  hipLaunchKernelGGL(dev::libm_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, fn, n, da.p, db.p, dout.p);
+  if (hipGetLastError() != hipSuccess || hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(RTW_ENODEV, "libm_kernel");
+  return RTW_OK;
 }
 
 int rtw_diag_sweep(int fn, uint32_t lo, uint32_t hi, uint64_t* counts, uint32_t* bad, uint32_t cap) {
   if (fn != 0 || lo > hi || !counts || (cap && !bad)) return fail(RTW_EINVAL, "bad arguments");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(RTW_ENODEV, "no HIP device visible");
-  unsigned long long* dn = nullptr;
-  uint32_t* dbad = nullptr;
-  int rc = RTW_OK;
-  if (hipMalloc((void**)&dn, 3 * sizeof(unsigned long long)) != hipSuccess ||
-      hipMalloc((void**)&dbad, (cap ? cap : 1) * sizeof(uint32_t)) != hipSuccess) {
-    rc = fail(RTW_ENOMEM, "hipMalloc(sweep)");
-  } else if (hipMemset(dn, 0, 3 * sizeof(unsigned long long)) != hipSuccess) {
-    rc = fail(RTW_ENODEV, "hipMemset(sweep)");
-  } else {
-    hipLaunchKernelGGL(dev::sweep_kernel, dim3(16384), dim3(256), 0, nullptr, fn, lo, hi, dn, dbad, cap);
-    unsigned long long h[3];
-    if (hipGetLastError() != hipSuccess || hipMemcpy(h, dn, sizeof h, hipMemcpyDeviceToHost) != hipSuccess ||
-        (cap && hipMemcpy(bad, dbad, cap * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)) {
-      rc = fail(RTW_ENODEV, "sweep_kernel");
-    } else {
-      counts[0] = h[0];
-      counts[1] = h[1];
-    }
-  }
-  if (dn) hipFree(dn);
-  if (dbad) hipFree(dbad);
-  return rc;
-}
-
-int rtw_unpack_tiles_device(int device, uint32_t w, uint32_t h, const uint32_t* d_tiles, uint32_t n_tiles,
-                            const float* d_packed, float* d_image, void* stream) {
-  if (!d_tiles || !d_packed || !d_image) return fail(RTW_EINVAL, "NULL argument");
-  DeviceGuard g;
-  if (device >= 0) HIPCHK(hipSetDevice(device), "hipSetDevice");
-  return enqueue_unpack(w, h, d_tiles, n_tiles, d_packed, d_image, stream);
+  DiagBuf<unsigned long long> dn;
+  DiagBuf<uint32_t> dbad;
+  if (!dn.alloc(3) || !dbad.alloc(cap ? cap : 1)) return fail(RTW_ENOMEM, "hipMalloc(sweep)");
+  if (hipMemset(dn.p, 0, 3 * sizeof(unsigned long long)) != hipSuccess) return fail(RTW_ENODEV, "hipMemset(sweep)");
+  hipLaunchKernelGGL(dev::sweep_kernel, dim3(16384), dim3(256), 0, nullptr, fn, lo, hi, dn.p, dbad.p, cap);
+  unsigned long long h[3];
+  if (hipGetLastError() != hipSuccess || hipMemcpy(h, dn.p, sizeof h, hipMemcpyDeviceToHost) != hipSuccess ||
+      (cap && hipMemcpy(bad, dbad.p, cap * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess))
+    return fail(RTW_ENODEV, "sweep_kernel");
+  counts[0] = h[0];
+  counts[1] = h[1];
+  return RTW_OK;
 }
 
 }  // extern "C"

@@ -18,14 +18,14 @@
 // clique's communicators (ncclGroupStart .. ncclGroupEnd) by that clique's own mutex, so host threads may
 // call rtw_render_multi concurrently on different scenes: RCCL communicators are not thread-safe, and two
 // interleaved grouped send/recv sequences on the same communicators could deadlock.
+// Each device's share is rendered by enqueue_render (rtw_kernel.hip); the device copies, the render calls' shared
+// opening (check_frame, need_copy) and collect_stats are rtw_render.cpp's.
 #include <dlfcn.h>
 #include <stdlib.h>
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
-#include <string.h>
 
 #include <algorithm>
-#include <chrono>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -106,12 +106,6 @@ std::vector<std::unique_ptr<Clique>>& cliques() {  // callers hold rccl_mutex()
   return c;
 }
 
-#define HIPOK(x, what)                                                              \
-  do {                                                                              \
-    hipError_t e_ = (x);                                                            \
-    if (e_ != hipSuccess) return fail(RTW_ENODEV, "%s: %s", what, hipGetErrorString(e_)); \
-  } while (0)
-
 // rank d of the clique is the communicator of the HIP device devs[d] (logical device d of the render)
 int get_clique(const std::vector<int>& devs, Clique** out) {
   std::lock_guard<std::mutex> lock(rccl_mutex());
@@ -144,7 +138,7 @@ extern "C" {
 int rtw_tile_partition(uint32_t w, uint32_t h, uint32_t n_parts, uint32_t part, uint32_t* ids, uint32_t cap,
                        uint32_t* n_ids) {
   if (!n_ids || n_parts == 0 || part >= n_parts || (cap && !ids)) return fail(RTW_EINVAL, "bad arguments");
-  const uint32_t nt = ((w + 7u) / 8u) * ((h + 7u) / 8u), per = (nt + n_parts - 1) / n_parts;
+  const uint32_t nt = (uint32_t)Frame{nullptr, nullptr, w, h}.tiles(), per = (nt + n_parts - 1) / n_parts;
   uint32_t k = 0;
   for (uint32_t t = part; t < nt; t += n_parts, ++k)
     if (k < cap) ids[k] = t;
@@ -156,9 +150,8 @@ int rtw_tile_partition(uint32_t w, uint32_t h, uint32_t n_parts, uint32_t part, 
 int rtw_render_multi(rtw_scene* s, int n_gpus, const rtw_camera* cam, const float bg[3], uint32_t w, uint32_t h,
                      uint32_t spp, uint32_t max_depth, uint64_t seed, float* out, rtw_stats* stats) {
   auto t0 = std::chrono::steady_clock::now();
-  if (!s || !cam || !bg || !out) return fail(RTW_EINVAL, "NULL argument");
-  if (!s->s.committed) return fail(RTW_ESTATE, "scene not committed");
-  if (w < 2 || h < 2) return fail(RTW_EINVAL, "image must be at least 2x2 (lib.rs:84-85 divides by w-1, h-1)");
+  const Frame f{cam, bg, w, h, spp, max_depth, seed};
+  if (int e = check_frame(s, f, out)) return e;
   s->s.multi_ms.clear();  //  a failed call leaves no stale timings behind
   s->s.multi_gather_ms = 0.0f;
   int ndev = 0;
@@ -167,56 +160,30 @@ int rtw_render_multi(rtw_scene* s, int n_gpus, const rtw_camera* cam, const floa
   const int n = n_gpus <= 0 ? ndev : n_gpus;
   if (n > ndev) return fail(RTW_EINVAL, "n_gpus %d > visible devices %d", n_gpus, ndev);
   std::vector<DeviceCopy*> cp(n);
-  for (int d = 0; d < n; ++d) {
-    cp[d] = nullptr;
-    for (DeviceCopy& c : s->s.dev)
-      if (c.device == d) cp[d] = &c;
-    if (!cp[d]) return fail(RTW_ENODEV, "scene was not committed to device %d (commit with device = -1)", d);
-  }
-  int prev = 0;
-  hipGetDevice(&prev);
-  struct Restore {
-    int d;
-    ~Restore() { hipSetDevice(d); }
-  } restore{prev};
-  std::vector<hipEvent_t> e0(n), e1(n);
+  for (int d = 0; d < n; ++d)
+    if (!(cp[d] = need_copy(s->s, d, " (commit with device = -1)"))) return RTW_ENODEV;
+  DeviceGuard g;
   for (int d = 0; d < n; ++d) {
     DeviceCopy& c = *cp[d];
-    HIPOK(hipSetDevice(c.phys), "hipSetDevice");
-    if (!c.stream) {
-      hipStream_t st;
-      HIPOK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "hipStreamCreate");
-      c.stream = st;
-    }
-    for (void*& e : c.ev)
-      if (!e) {
-        hipEvent_t x;
-        HIPOK(hipEventCreate(&x), "hipEventCreate");
-        e = x;
-      }
-    e0[d] = static_cast<hipEvent_t>(c.ev[0]);
-    e1[d] = static_cast<hipEvent_t>(c.ev[1]);
+    HIPCHK(hipSetDevice(c.phys), "hipSetDevice");
+    if (!c.stream) HIPCHK(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking), "hipStreamCreate");
+    if (int e = copy_events(c)) return e;
   }
-  const uint32_t tiles_x = (w + 7u) / 8u, nt = tiles_x * ((h + 7u) / 8u);
+  const uint32_t nt = (uint32_t)f.tiles();
   const size_t frame_bytes = (size_t)w * h * 3 * sizeof(float);
 
   if (n == 1) {  // one device: rtw_render's path (the whole frame straight into the image), no RCCL
     DeviceCopy& c = *cp[0];
-    HIPOK(hipSetDevice(c.phys), "hipSetDevice");
-    hipStream_t st = static_cast<hipStream_t>(c.stream);
+    HIPCHK(hipSetDevice(c.phys), "hipSetDevice");
     if (int e = grow(c.image, frame_bytes)) return e;
-    TileSet all;
-    all.n = nt;
-    if (int e = enqueue_render(s->s, c, cam, bg, w, h, spp, max_depth, seed, all, static_cast<float*>(c.image.p), st, 0,
-                               e0[0], e1[0]))
-      return e;
-    rtw_stats st1;
-    memset(&st1, 0, sizeof st1);
-    if (int e = collect_stats(c, st, e0[0], e1[0], (uint64_t)w * h * spp, &st1)) return e;
-    HIPOK(hipMemcpy(out, c.image.p, frame_bytes, hipMemcpyDeviceToHost), "hipMemcpy(image)");
+    const TileSet all{nullptr, 0, 1, nt};
+    if (int e = enqueue_render(s->s, c, f, all, static_cast<float*>(c.image.p), c.stream, 0, c.ev[0], c.ev[1])) return e;
+    rtw_stats st1{};
+    if (int e = collect_stats(c, c.stream, c.ev[0], c.ev[1], f.paths(), &st1)) return e;
+    HIPCHK(hipMemcpy(out, c.image.p, frame_bytes, hipMemcpyDeviceToHost), "hipMemcpy(image)");
     s->s.multi_ms.assign(1, (float)st1.kernel_ms);
     s->s.multi_gather_ms = 0.0f;
-    st1.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    st1.total_ms = ms_since(t0);
     if (stats) *stats = st1;
     return RTW_OK;
   }
@@ -239,44 +206,32 @@ int rtw_render_multi(rtw_scene* s, int n_gpus, const rtw_camera* cam, const floa
   // packed buffer on its own stream, all enqueued before any wait
   for (int d = 0; d < n; ++d) {
     DeviceCopy& c = *cp[d];
-    HIPOK(hipSetDevice(c.phys), "hipSetDevice");
-    hipStream_t st = static_cast<hipStream_t>(c.stream);
+    HIPCHK(hipSetDevice(c.phys), "hipSetDevice");
     if (int e = grow(c.packed, slot_floats * sizeof(float))) return e;
-    TileSet mt;
-    mt.first = (uint32_t)d;
-    mt.stride = (uint32_t)n;
-    mt.n = mine[d];
-    mt.packed = true;
-    if (int e = enqueue_render(s->s, c, cam, bg, w, h, spp, max_depth, seed, mt, static_cast<float*>(c.packed.p), st, 0,
-                               e0[d], e1[d]))
-      return e;
+    const TileSet mt{nullptr, (uint32_t)d, (uint32_t)n, mine[d], true};
+    if (int e = enqueue_render(s->s, c, f, mt, static_cast<float*>(c.packed.p), c.stream, 0, c.ev[0], c.ev[1])) return e;
   }
   // 2. one RCCL gather to device 0 (each device's send waits for its render on the same stream)
   DeviceCopy& c0 = *cp[0];
-  HIPOK(hipSetDevice(c0.phys), "hipSetDevice");
-  hipStream_t st0 = static_cast<hipStream_t>(c0.stream);
+  HIPCHK(hipSetDevice(c0.phys), "hipSetDevice");
+  const hipStream_t st0 = c0.stream;
   if (int e = grow(c0.gathered, (size_t)n * slot_floats * sizeof(float))) return e;
   if (int e = grow(c0.gather_ids, all.size() * sizeof(uint32_t))) return e;
   if (int e = grow(c0.image, (size_t)w * h * 3 * sizeof(float))) return e;
-  HIPOK(hipMemcpyAsync(c0.gather_ids.p, all.data(), all.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st0),
-        "hipMemcpyAsync(gather ids)");
+  HIPCHK(hipMemcpyAsync(c0.gather_ids.p, all.data(), all.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st0),
+         "hipMemcpyAsync(gather ids)");
   float* gathered = static_cast<float*>(c0.gathered.p);
   // device 0's gather time: its stream from the end of its own render to the last tile's arrival (so it
   // includes waiting for the slowest device), rtw_render_multi_times
-  for (void*& e : c0.gev)
-    if (!e) {
-      hipEvent_t x;
-      HIPOK(hipEventCreate(&x), "hipEventCreate");
-      e = x;
-    }
-  HIPOK(hipEventRecord(static_cast<hipEvent_t>(c0.gev[0]), st0), "hipEventRecord");
+  for (hipEvent_t& e : c0.gev)
+    if (int rc = ensure_event(e)) return rc;
+  HIPCHK(hipEventRecord(c0.gev[0], st0), "hipEventRecord");
   {
     std::lock_guard<std::mutex> lock(clique->mu);  // one grouped send/recv on these communicators at a time
     const ncclResult_t g0 = r.group_start();
     if (g0 != ncclSuccess) return fail(RTW_ENODEV, "ncclGroupStart: %s", r.error_string(g0));
     for (int d = 0; d < n; ++d) {
-      hipStream_t st = static_cast<hipStream_t>(cp[d]->stream);
-      const ncclResult_t a = r.send(cp[d]->packed.p, slot_floats, ncclFloat32, 0, (*comms)[d], st);
+      const ncclResult_t a = r.send(cp[d]->packed.p, slot_floats, ncclFloat32, 0, (*comms)[d], cp[d]->stream);
       if (a != ncclSuccess) {
         r.group_end();
         return fail(RTW_ENODEV, "ncclSend: %s", r.error_string(a));
@@ -292,40 +247,37 @@ int rtw_render_multi(rtw_scene* s, int n_gpus, const rtw_camera* cam, const floa
     const ncclResult_t g1 = r.group_end();
     if (g1 != ncclSuccess) return fail(RTW_ENODEV, "ncclGroupEnd: %s", r.error_string(g1));
   }
-  HIPOK(hipSetDevice(c0.phys), "hipSetDevice");
-  HIPOK(hipEventRecord(static_cast<hipEvent_t>(c0.gev[1]), st0), "hipEventRecord");
+  HIPCHK(hipSetDevice(c0.phys), "hipSetDevice");
+  HIPCHK(hipEventRecord(c0.gev[1], st0), "hipEventRecord");
   // 3. device 0 scatters the gathered tiles into the frame and copies it out
-  HIPOK(hipSetDevice(c0.phys), "hipSetDevice");
+  HIPCHK(hipSetDevice(c0.phys), "hipSetDevice");
   if (int e = enqueue_unpack(w, h, static_cast<uint32_t*>(c0.gather_ids.p), (uint32_t)all.size(), gathered,
                              static_cast<float*>(c0.image.p), st0))
     return e;
-  HIPOK(hipMemcpyAsync(out, c0.image.p, (size_t)w * h * 3 * sizeof(float), hipMemcpyDeviceToHost, st0),
-        "hipMemcpyAsync(image)");
-  rtw_stats tot;
-  memset(&tot, 0, sizeof tot);
+  HIPCHK(hipMemcpyAsync(out, c0.image.p, (size_t)w * h * 3 * sizeof(float), hipMemcpyDeviceToHost, st0),
+         "hipMemcpyAsync(image)");
+  rtw_stats tot{};
   std::vector<float> dev_ms(n);
   for (int d = 0; d < n; ++d) {
-    HIPOK(hipSetDevice(cp[d]->phys), "hipSetDevice");
-    rtw_stats st;
-    memset(&st, 0, sizeof st);
-    if (int e = collect_stats(*cp[d], cp[d]->stream, e0[d], e1[d], 0, &st)) return e;
+    HIPCHK(hipSetDevice(cp[d]->phys), "hipSetDevice");
+    rtw_stats st{};
+    if (int e = collect_stats(*cp[d], cp[d]->stream, cp[d]->ev[0], cp[d]->ev[1], 0, &st)) return e;
     tot.rays += st.rays;
     tot.kernel_ms = std::max(tot.kernel_ms, st.kernel_ms);  // the devices run concurrently
     dev_ms[d] = (float)st.kernel_ms;
   }
   float gms = 0.0f;
-  HIPOK(hipSetDevice(c0.phys), "hipSetDevice");
-  HIPOK(hipEventElapsedTime(&gms, static_cast<hipEvent_t>(c0.gev[0]), static_cast<hipEvent_t>(c0.gev[1])),
-        "hipEventElapsedTime(gather)");
+  HIPCHK(hipSetDevice(c0.phys), "hipSetDevice");
+  HIPCHK(hipEventElapsedTime(&gms, c0.gev[0], c0.gev[1]), "hipEventElapsedTime(gather)");
   s->s.multi_ms = dev_ms;
   s->s.multi_gather_ms = gms;
-  tot.paths = (uint64_t)w * h * spp;
-  tot.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  tot.paths = f.paths();
+  tot.total_ms = ms_since(t0);
   if (stats) *stats = tot;
   return RTW_OK;
 }
 
-// Test hook: n logical devices on physical device 0 (upload in rtw_kernel.hip; include/rtw.h)
+// Test hook: n logical devices on physical device 0 (upload in rtw_render.cpp; include/rtw.h)
 int rtw_diag_alias_devices(rtw_scene* s, int n) {
   if (!s) return fail(RTW_EINVAL, "NULL argument");
   if (s->s.committed) return fail(RTW_ESTATE, "scene already committed (alias the devices before the commit)");

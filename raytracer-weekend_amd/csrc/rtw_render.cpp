@@ -1,0 +1,410 @@
+// rtw_render.cpp — the host render runtime behind the C-ABI's device half: the scene's device copies (upload, release,
+// the grow-only buffers), the render calls' shared opening (check_frame, need_copy), statistics, the traversal guard's
+// error word, and the render / status entry points of one device.  Plain HIP runtime API: the kernels, which variant a
+// scene runs and how a render is enqueued are rtw_kernel.hip's (enqueue_render, enqueue_unpack); the render over
+// several devices is rtw_multi.cpp's.
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+
+#include "../../include/rtw.h"
+#include "rtw_scene.hpp"
+
+namespace rtw {
+
+template <class T>
+static size_t put(std::vector<uint8_t>& blob, const std::vector<T>& v) {
+  size_t off = (blob.size() + 255) & ~(size_t)255;
+  blob.resize(off + sizeof(T) * v.size());
+  if (!v.empty()) memcpy(blob.data() + off, v.data(), sizeof(T) * v.size());
+  return off;
+}
+
+int upload(Scene& s, int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(RTW_ENODEV, "no HIP device visible (the render core has no CPU fallback)");
+  const int nlog = s.alias_n > 0 ? s.alias_n : ndev;  // logical devices (rtw_diag_alias_devices: all on 0)
+  if (device >= nlog) return fail(RTW_EINVAL, "device %d >= device count %d", device, nlog);
+  const Flat& f = s.flat;
+  std::vector<uint8_t> blob;
+  // the far-origin record sits DEVFAR_BACK bytes before the prim table (trace_begin derives it from S.prims)
+  DevFar far = f.far;
+  const size_t o_nodes = put(blob, f.nodes4), o_far = put(blob, std::vector<DevFar>{far});
+  size_t o_prims = put(blob, f.prims), o_always = put(blob, f.always);
+  if (o_prims - o_far != DEVFAR_BACK) return fail(RTW_EINVAL, "internal: far record not %u B before the prims", DEVFAR_BACK);
+  reinterpret_cast<DevFar*>(blob.data() + o_far)->nodes_back = (uint32_t)(o_prims - o_nodes);
+  size_t o_tsh = put(blob, f.tshade), o_inst = put(blob, f.insts), o_mat = put(blob, f.mats);
+  size_t o_tex = put(blob, f.texs), o_texel = put(blob, f.texels), o_perlin = put(blob, f.perlins);
+  size_t o_shade = put(blob, f.shade), o_hnodes = put(blob, f.nodes4h), o_groups = put(blob, f.lgroups);
+  blob.resize((blob.size() + 255) & ~(size_t)255);
+  int d0 = device >= 0 ? device : 0, d1 = device >= 0 ? device + 1 : nlog;
+  DeviceGuard g;
+  // one device's copy, built in place in s.dev: release() frees whatever a failed step leaves behind
+  auto fill = [&](DeviceCopy& c, int d) -> int {
+    const int phys = s.alias_n > 0 ? 0 : d;
+    c.device = d;
+    c.phys = phys;
+    HIPCHK(hipSetDevice(phys), "hipSetDevice");
+    c.bytes = blob.size();
+    HIPCHK(hipMalloc(&c.block, c.bytes), "hipMalloc(scene)");
+    HIPCHK(hipMemcpy(c.block, blob.data(), c.bytes, hipMemcpyHostToDevice), "hipMemcpy(scene)");
+    HIPCHK(hipMalloc((void**)&c.counters, COUNTER_WORDS * sizeof(unsigned long long)), "hipMalloc(counters)");
+    // the sticky traversal-error word lives in host memory the kernel writes through (coherent,
+    // mapped): the host reads it without a device round trip, also for renders it did not wait for
+    HIPCHK(hipHostMalloc((void**)&c.err_host, 64, hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc(error word)");
+    *(volatile uint32_t*)c.err_host = 0u;
+    uint8_t* base = (uint8_t*)c.block;
+    c.scene.nodes = (const DevNode4*)(base + o_nodes);
+    c.scene.hnodes = f.nodes4h.empty() ? nullptr : (const DevNode4h*)(base + o_hnodes);
+    c.scene.prims = (const DevPrim*)(base + o_prims);
+    c.scene.always = (const uint32_t*)(base + o_always);
+    c.scene.tshade = (const DevTriShade*)(base + o_tsh);
+    c.scene.insts = (const DevInst*)(base + o_inst);
+    c.scene.mats = (const DevMat*)(base + o_mat);
+    c.scene.texs = (const DevTex*)(base + o_tex);
+    c.scene.texels = (const uint8_t*)(base + o_texel);
+    c.scene.perlins = (const DevPerlin*)(base + o_perlin);
+    c.scene.shade = (const DevShade*)(base + o_shade);
+    c.scene.lgroups = (const DevGroup*)(base + o_groups);
+    c.scene.n_lgroups = (uint32_t)f.lgroups.size();
+    c.scene.n_nodes = (uint32_t)f.nodes4.size();
+    c.scene.n_prims = (uint32_t)f.prims.size();
+    c.scene.n_always = (uint32_t)f.always.size();
+    c.scene.n_insts = (uint32_t)f.insts.size();
+    c.scene.msphere_unit = f.msphere_unit;
+    c.scene.uni_inst = f.uni_inst;
+    c.scene.bvh_tri = f.bvh_tri;  // knob RTW_TRI_LEAF (rtw_flatten.cpp)
+    c.scene.tri_inst = f.tri_inst;
+    c.scene.rect_fast = f.rect_fast;
+    memcpy(c.scene.uni_off, f.uni_off, sizeof f.uni_off);
+    c.scene.far_check = f.far_check;
+    return RTW_OK;
+  };
+  for (int d = d0; d < d1; ++d) {
+    s.dev.emplace_back();
+    if (int e = fill(s.dev.back(), d)) {
+      release(s);
+      return e;
+    }
+  }
+  return RTW_OK;
+}
+
+static void free_buf(DevBuf& b) {
+  if (b.p) hipFree(b.p);
+  b.p = nullptr;
+  b.cap = 0;
+}
+
+void release(Scene& s) {
+  for (DeviceCopy& c : s.dev) {
+    if (hipSetDevice(c.phys) != hipSuccess) continue;
+    if (c.block) hipFree(c.block);
+    if (c.counters) hipFree(c.counters);
+    if (c.err_host) hipHostFree(c.err_host);
+    for (DevBuf* b : {&c.sbuf, &c.spill, &c.image, &c.tiles, &c.packed, &c.gathered, &c.gather_ids}) free_buf(*b);
+    for (hipEvent_t e : {c.ev[0], c.ev[1], c.gev[0], c.gev[1]})
+      if (e) hipEventDestroy(e);
+    if (c.stream) hipStreamDestroy(c.stream);
+    for (auto& pair : c.kev)
+      for (hipEvent_t e : pair)
+        if (e) hipEventDestroy(e);
+  }
+  s.dev.clear();
+}
+
+DeviceCopy* find_copy(Scene& s, int device) {
+  for (DeviceCopy& c : s.dev)
+    if (c.device == device || device < 0) return &c;
+  return nullptr;
+}
+
+int grow(DevBuf& b, size_t bytes) {
+  if (bytes <= b.cap) return RTW_OK;
+  free_buf(b);
+  HIPCHK(hipMalloc(&b.p, bytes), "hipMalloc(render buffer)");
+  b.cap = bytes;
+  return RTW_OK;
+}
+
+int check_frame(const rtw_scene* s, const Frame& f, bool out) {
+  if (!s || !f.cam || !f.bg || !out) return fail(RTW_EINVAL, "NULL argument");
+  if (!s->s.committed) return fail(RTW_ESTATE, "scene not committed");
+  if (f.w < 2 || f.h < 2) return fail(RTW_EINVAL, "image must be at least 2x2 (lib.rs:84-85 divides by w-1, h-1)");
+  return RTW_OK;
+}
+
+DeviceCopy* need_copy(Scene& s, int device, const char* hint) {
+  DeviceCopy* c = find_copy(s, device);
+  if (c) return c;
+  if (hint) fail(RTW_ENODEV, "scene was not committed to device %d%s", device, hint);
+  else fail(RTW_ENODEV, "scene has no device copy");
+  return nullptr;
+}
+
+int copy_events(DeviceCopy& c) {
+  for (hipEvent_t& e : c.ev)
+    if (int rc = ensure_event(e)) return rc;
+  return RTW_OK;
+}
+
+// RN(1 / b) for an integer-valued b in [1, 2^24): the float nearest 1 / b, chosen among the neighbours of
+// the double quotient by the exact residual |1 - y b| (y b is exact in double: 24 x 24 bits)
+float recip_rn(float b) {
+  float y = (float)(1.0 / (double)b), best = y;
+  double e = fabs(1.0 - (double)y * (double)b);
+  for (float c : {nextafterf(y, 0.0f), nextafterf(y, 2.0f)}) {
+    const double ec = fabs(1.0 - (double)c * (double)b);
+    if (ec < e) { e = ec; best = c; }
+  }
+  return best;
+}
+
+int check_guard(DeviceCopy& c) {
+  volatile uint32_t* e = c.err_host;
+  if (e && *e) {
+    *e = 0u;
+    return fail(RTW_EINVAL, "a path kernel on device %d tripped its BVH traversal guard (corrupt tree?): the frame "
+                "it rendered is invalid", c.device);
+  }
+  return RTW_OK;
+}
+
+int collect_stats(DeviceCopy& c, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, uint64_t paths, rtw_stats* st) {
+  HIPCHK(hipStreamSynchronize(stream), "render_kernel");
+  unsigned long long cnt[32];
+  HIPCHK(hipMemcpy(cnt, c.counters, sizeof cnt, hipMemcpyDeviceToHost), "hipMemcpy(counters)");
+  float ms = 0.f;
+  if (ev0 && ev1) HIPCHK(hipEventElapsedTime(&ms, ev0, ev1), "hipEventElapsedTime");
+  if (int e = check_guard(c)) return e;
+  st->rays = cnt[0];
+  st->paths = paths;
+  st->kernel_ms = ms;
+  st->node_visits = cnt[1];
+  st->prim_tests = cnt[2];
+  for (int k = 0; k < 6; ++k) st->prim_tests_by_type[k] = cnt[3 + k];
+  for (int k = 0; k < 6; ++k) st->simd[k] = cnt[9 + k];
+  for (int k = 0; k < 4; ++k) st->phase_cycles[k] = cnt[16 + k];
+  st->boxes_tested = cnt[15];
+  for (int k = 0; k < 4; ++k) st->sub_cycles[k] = cnt[20 + k];
+  return RTW_OK;
+}
+
+// rtw_render_device and rtw_render_device_strided behind their tile sets
+static int render_device(rtw_scene* s, int device, const Frame& f, const TileSet& ts, float* d_out, hipStream_t stream,
+                         uint32_t flags, rtw_stats* stats) {
+  auto t0 = std::chrono::steady_clock::now();
+  if (int e = check_frame(s, f, d_out)) return e;
+  DeviceCopy* c = need_copy(s->s, device);
+  if (!c) return RTW_ENODEV;
+  DeviceGuard g;
+  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
+  if (stats)
+    if (int e = copy_events(*c)) return e;
+  const hipEvent_t e0 = stats ? c->ev[0] : nullptr, e1 = stats ? c->ev[1] : nullptr;
+  int rc = enqueue_render(s->s, *c, f, ts, d_out, stream, flags, e0, e1);
+  if (rc == RTW_OK && stats) {
+    rtw_stats st{};
+    rc = collect_stats(*c, stream, e0, e1, (uint64_t)ts.n * 64u * f.spp, &st);
+    st.total_ms = ms_since(t0);
+    *stats = st;
+  }
+  return rc;
+}
+
+}  // namespace rtw
+
+using namespace rtw;
+
+extern "C" {
+
+int rtw_device_count(void) {
+  int n = 0;
+  return hipGetDeviceCount(&n) == hipSuccess ? n : 0;
+}
+
+int rtw_render(rtw_scene* s, const rtw_camera* cam, const float bg[3], uint32_t w, uint32_t h,
+               uint32_t spp, uint32_t max_depth, uint64_t seed, float* out, rtw_stats* stats) {
+  auto t0 = std::chrono::steady_clock::now();
+  const Frame f{cam, bg, w, h, spp, max_depth, seed};
+  if (int e = check_frame(s, f, out)) return e;
+  DeviceCopy* c = need_copy(s->s, -1, nullptr);
+  if (!c) return RTW_ENODEV;
+  DeviceGuard g;
+  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
+  const size_t bytes = (size_t)w * h * 3 * sizeof(float);
+  if (int e = copy_events(*c)) return e;
+  if (int e = grow(c->image, bytes)) return e;  // kept for the next frame (no per-call hipMalloc)
+  float* d_out = static_cast<float*>(c->image.p);
+  rtw_stats st{};
+  const TileSet all{nullptr, 0, 1, (uint32_t)f.tiles()};
+  int rc = enqueue_render(s->s, *c, f, all, d_out, nullptr, 0, c->ev[0], c->ev[1]);
+  if (rc == RTW_OK) rc = collect_stats(*c, nullptr, c->ev[0], c->ev[1], f.paths(), &st);
+  if (rc == RTW_OK && hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost) != hipSuccess)
+    rc = fail(RTW_ENODEV, "hipMemcpy(image)");
+  st.total_ms = ms_since(t0);
+  if (stats) *stats = st;
+  return rc;
+}
+
+int rtw_render_device(rtw_scene* s, int device, const rtw_camera* cam, const float bg[3], uint32_t w,
+                      uint32_t h, uint32_t spp, uint32_t max_depth, uint64_t seed, const uint32_t* d_tiles,
+                      uint32_t n_tiles, float* d_out, void* stream, uint32_t flags, rtw_stats* stats) {
+  const Frame f{cam, bg, w, h, spp, max_depth, seed};
+  const TileSet ts{d_tiles, 0, 1, d_tiles ? n_tiles : (uint32_t)f.tiles()};
+  return render_device(s, device, f, ts, d_out, abi_stream(stream), flags, stats);
+}
+
+int rtw_render_device_strided(rtw_scene* s, int device, const rtw_camera* cam, const float bg[3], uint32_t w,
+                              uint32_t h, uint32_t spp, uint32_t max_depth, uint64_t seed, uint32_t first_tile,
+                              uint32_t tile_stride, uint32_t n_tiles, float* d_out, void* stream, uint32_t flags,
+                              rtw_stats* stats) {
+  const Frame f{cam, bg, w, h, spp, max_depth, seed};
+  const uint64_t nt = f.tiles();
+  if (tile_stride == 0 || (n_tiles && first_tile + (uint64_t)(n_tiles - 1) * tile_stride >= nt))
+    return fail(RTW_EINVAL, "tiles %u + k * %u (k < %u) leave the frame's %llu tiles", first_tile, tile_stride, n_tiles,
+                (unsigned long long)nt);
+  const TileSet ts{nullptr, first_tile, tile_stride, n_tiles, true};
+  return render_device(s, device, f, ts, d_out, abi_stream(stream), flags, stats);
+}
+
+int rtw_render_status(rtw_scene* s, int device) {
+  if (!s) return fail(RTW_EINVAL, "NULL argument");
+  DeviceCopy* c = need_copy(s->s, device);
+  if (!c) return RTW_ENODEV;
+  DeviceGuard g;
+  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
+  HIPCHK(hipDeviceSynchronize(), "render (hipDeviceSynchronize)");
+  return check_guard(*c);
+}
+
+// Test hook: overwrite the first two node4s of the device copy with a cycle (node 0 -> node 1 -> node 1
+// ..., every box infinite, in both the 32-bit child words and the 16-bit codes), so that every ray's
+// walk trips the traversal guard.  The host tables are untouched; renders of this copy are invalid.
+int rtw_diag_corrupt_bvh(rtw_scene* s, int device) {
+  if (!s) return fail(RTW_EINVAL, "NULL argument");
+  if (!s->s.committed) return fail(RTW_ESTATE, "scene not committed");
+  DeviceCopy* c = need_copy(s->s, device);
+  if (!c) return RTW_ENODEV;
+  if (c->scene.n_nodes < 2) return fail(RTW_EINVAL, "the scene's BVH has %u node4s (needs 2)", c->scene.n_nodes);
+  DevNode4 nd[2];
+  memset(nd, 0, sizeof nd);
+  for (DevNode4& n : nd) {
+    for (int k = 0; k < 4; ++k) {
+      const float lo = k ? INFINITY : -1e30f, hi = k ? -INFINITY : 1e30f;  // slots 1-3 empty
+      n.lo_x[k] = n.lo_y[k] = n.lo_z[k] = lo;
+      n.hi_x[k] = n.hi_y[k] = n.hi_z[k] = hi;
+    }
+    n.child[0] = 1;
+    n.code[0] = 1u;
+  }
+  DeviceGuard g;
+  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
+  HIPCHK(hipMemcpy(const_cast<DevNode4*>(c->scene.nodes), nd, sizeof nd, hipMemcpyHostToDevice), "hipMemcpy(nodes)");
+  if (c->scene.hnodes) {  // the half-precision table too: slot 0 = [-65504, +inf) on every axis, slots 1-3 empty
+    DevNode4h hn[2];
+    memset(hn, 0, sizeof hn);
+    for (DevNode4h& n : hn) {
+      for (uint16_t* ax : {&n.x[0][0], &n.y[0][0], &n.z[0][0]})
+        for (int k = 0; k < 4; ++k) {
+          const uint16_t lo = k ? 0x7C00 : 0x0000, hi = k ? 0xFC00 : 0x7C00;
+          ax[k] = lo; ax[4 + k] = hi; ax[8 + k] = hi; ax[12 + k] = lo;
+        }
+      n.origin[0] = n.origin[1] = n.origin[2] = 0xFBFF;  // -65504
+      n.code[0] = 1;
+    }
+    HIPCHK(hipMemcpy(const_cast<DevNode4h*>(c->scene.hnodes), hn, sizeof hn, hipMemcpyHostToDevice), "hipMemcpy(hnodes)");
+  }
+  return RTW_OK;
+}
+
+int rtw_render_stream(rtw_scene* s, const rtw_camera* cam, const float bg[3], uint32_t w, uint32_t h, uint32_t spp,
+                      uint32_t max_depth, uint64_t seed, uint32_t band_rows, rtw_pixel_sink sink, void* user,
+                      rtw_stats* stats) {
+  auto t0 = std::chrono::steady_clock::now();
+  const Frame f{cam, bg, w, h, spp, max_depth, seed};
+  if (int e = check_frame(s, f, sink)) return e;
+  DeviceCopy* c = need_copy(s->s, -1, nullptr);
+  if (!c) return RTW_ENODEV;
+  const uint32_t tiles_x = f.tiles_x(), tiles_y = (h + 7u) / 8u;
+  const uint32_t band_ty = std::max(1u, ((band_rows ? band_rows : 64u) + 7u) / 8u);  // tile rows per band
+  DeviceGuard g;
+  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
+  const size_t band_tiles = (size_t)band_ty * tiles_x;
+  if (int e = grow(c->packed, band_tiles * 64 * 3 * sizeof(float))) return e;
+  float* d_packed = static_cast<float*>(c->packed.p);
+  if (int e = copy_events(*c)) return e;
+  int rc = RTW_OK;
+  std::vector<float> packed(band_tiles * 64 * 3);
+  std::vector<rtw_pixel> px;
+  rtw_stats tot{};
+  for (uint32_t ty0 = 0; rc == RTW_OK && ty0 < tiles_y; ty0 += band_ty) {
+    const uint32_t nty = std::min(band_ty, tiles_y - ty0), nt = nty * tiles_x;
+    // tile row ty = output rows [8 ty, 8 ty + 8): the band's tiles are consecutive
+    const TileSet band{nullptr, ty0 * tiles_x, 1, nt, true};
+    rc = enqueue_render(s->s, *c, f, band, d_packed, nullptr, 0, c->ev[0], c->ev[1]);
+    rtw_stats st{};
+    if (rc == RTW_OK) rc = collect_stats(*c, nullptr, c->ev[0], c->ev[1], 0, &st);
+    if (rc == RTW_OK && hipMemcpy(packed.data(), d_packed, (size_t)nt * 64 * 3 * sizeof(float),
+                                  hipMemcpyDeviceToHost) != hipSuccess)
+      rc = fail(RTW_ENODEV, "hipMemcpy(band)");
+    if (rc != RTW_OK) break;
+    tot.rays += st.rays;
+    tot.kernel_ms += st.kernel_ms;
+    // emit rows of this band in reference order: output row r <-> j = h-1-r, columns 0..w-1
+    const uint32_t r0 = ty0 * 8u, r1 = std::min(h, (ty0 + nty) * 8u);
+    px.clear();
+    for (uint32_t r = r0; r < r1; ++r)
+      for (uint32_t i = 0; i < w; ++i) {
+        const size_t slot = (size_t)(r / 8u - ty0) * tiles_x + i / 8u, lane = (r % 8u) * 8u + (i % 8u);
+        const float* v = &packed[(slot * 64 + lane) * 3];
+        px.push_back(rtw_pixel{h - 1u - r, i, {v[0], v[1], v[2]}});
+      }
+    if (int e = sink(px.data(), (uint32_t)px.size(), user)) rc = e;
+  }
+  tot.paths = f.paths();
+  tot.total_ms = ms_since(t0);
+  if (stats) *stats = tot;
+  return rc;
+}
+
+int rtw_path_kernel_times(rtw_scene* s, int device, float* ms, uint32_t max_n) {
+  if (!s || (!ms && max_n)) return fail(RTW_EINVAL, "NULL argument");
+  DeviceCopy* c = need_copy(s->s, device);
+  if (!c) return RTW_ENODEV;
+  DeviceGuard g;
+  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
+  const uint32_t n = std::min(c->kev_count, max_n);
+  int rc = (int)n;
+  for (uint32_t q = 0; q < n; ++q) {  // the n most recent, oldest first
+    const hipEvent_t* e = c->kev[(c->kev_head + 64u - n + q) % 64u];
+    hipError_t err = hipEventSynchronize(e[1]);
+    if (err == hipSuccess) err = hipEventElapsedTime(&ms[q], e[0], e[1]);
+    if (err != hipSuccess) {
+      rc = fail(RTW_ENODEV, "path-kernel events: %s", hipGetErrorString(err));
+      break;
+    }
+  }
+  c->kev_count = 0;
+  if (rc >= 0 && n)  // the launches waited for: report a tripped traversal guard (its frame is invalid)
+    if (int e = check_guard(*c)) rc = e;
+  return rc;
+}
+
+int rtw_diag_recip(uint32_t n, const float* b, float* out) {
+  if (n && (!b || !out)) return fail(RTW_EINVAL, "NULL argument");
+  for (uint32_t k = 0; k < n; ++k) out[k] = recip_rn(b[k]);
+  return RTW_OK;
+}
+
+int rtw_unpack_tiles_device(int device, uint32_t w, uint32_t h, const uint32_t* d_tiles, uint32_t n_tiles,
+                            const float* d_packed, float* d_image, void* stream) {
+  if (!d_tiles || !d_packed || !d_image) return fail(RTW_EINVAL, "NULL argument");
+  DeviceGuard g;
+  if (device >= 0) HIPCHK(hipSetDevice(device), "hipSetDevice");
+  return enqueue_unpack(w, h, d_tiles, n_tiles, d_packed, d_image, abi_stream(stream));
+}
+
+}  // extern "C"

@@ -2,10 +2,13 @@
 //
 // The graph keeps the reference's Hittable tree shape (raytracer_weekend_lib/src/hittable/,
 // bvh.rs) so that rtw_scene_dump() can hand the exact hierarchy to the test oracle; the
-// flattener (rtw_flatten.cpp) turns it into the device layout of rtw_device.hpp.
+// flattener (rtw_flatten.cpp) turns it into the device layout of rtw_device.hpp.  Below it: the scene's device
+// copies, and what the host sources that call HIP share (the check macro, the device guard, Frame, TileSet).
 #pragma once
+#include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include <chrono>
 #include <string>
 #include <vector>
 
@@ -103,17 +106,16 @@ struct DeviceCopy {
   uint32_t* err_host = nullptr;
   DevBuf sbuf;                             // ordered per-sample radiance (rgb floats per path of a pass)
   DevBuf spill;                            // traversal-stack overflow (trees deeper than the LDS stack)
-  void* kev[64][2] = {};                   // hipEvent_t pairs around path-kernel launches (ring,
-                                           // rtw_path_kernel_times)
+  hipEvent_t kev[64][2] = {};              // pairs around path-kernel launches (ring, rtw_path_kernel_times)
   uint32_t kev_head = 0, kev_count = 0;
   int grid[2] = {0, 0};                    // resident path_kernel grid (plain, counting) of the
-  void* grid_fn[2] = {nullptr, nullptr};   // variant it was computed for (knobs may switch variants)
+  const void* grid_fn[2] = {nullptr, nullptr};  // variant it was computed for (knobs may switch variants)
   // device buffers kept across render calls (grown, never shrunk; freed by release()): a
   // 30-camera animation through rtw_render does no hipMalloc after the first frame
   DevBuf image, tiles, packed, gathered, gather_ids;
-  void* ev[2] = {nullptr, nullptr};        // hipEvent_t pair timing rtw_render / multi calls
-  void* stream = nullptr;                  // hipStream_t of rtw_render_multi on this device
-  void* gev[2] = {nullptr, nullptr};       // hipEvent_t pair around rtw_render_multi's gather (device 0)
+  hipEvent_t ev[2] = {nullptr, nullptr};   // pair timing rtw_render / multi calls (copy_events)
+  hipStream_t stream = nullptr;            // rtw_render_multi's stream on this device
+  hipEvent_t gev[2] = {nullptr, nullptr};  // pair around rtw_render_multi's gather (device 0)
 };
 
 struct Scene {
@@ -135,18 +137,46 @@ struct Scene {
   Scene() { nodes.push_back(Node{NK_LIST, {}}); }
 };
 
-// rtw_flatten.cpp
-int flatten(Scene& s);
-// rtw_scene.cpp
-std::string dump_scene(const Scene& s);
-// rtw_kernel.hip
-int upload(Scene& s, int device);
-void release(Scene& s);
-DeviceCopy* find_copy(Scene& s, int device);  // device < 0: the first copy
-int grow(DevBuf& b, size_t bytes);            // current device; contents not kept
-// field 0-7 (stack, spill, occ, feat, blk, ncap, half, s16) of the path-kernel configuration the current
-// environment selects for the committed scene (rtw_scene_info 16-23); host only, no device needed
-int64_t selected_kernel_info(const Scene& s, int field);
+// thread-local error reporting (rtw_capi.cpp)
+int fail(int code, const char* fmt, ...);
+// A tuning knob's value (RTW_OCC, RTW_BATCH, RTW_LIST_MAX, ...: DESIGN.md §4), or NULL.  The knobs select
+// kernel variants and scheduling parameters for A/B measurements; they are read only when RTW_TUNING=1, so a
+// process that inherits a stray variable still runs the default (measured-best) kernels.  A knob set without
+// the gate is ignored with one warning on stderr (rtw_capi.cpp).
+const char* tuning_env(const char* name);
+
+// ---- small things every HIP-calling source shares (rtw_render.cpp, rtw_multi.cpp, rtw_kernel.hip)
+#define HIPCHK(x, what)                                                                        \
+  do {                                                                                         \
+    hipError_t e_ = (x);                                                                       \
+    if (e_ != hipSuccess) return rtw::fail(RTW_ENODEV, "%s: %s", what, hipGetErrorString(e_)); \
+  } while (0)
+// restores the caller's current device on every return path
+struct DeviceGuard {
+  int prev = 0;
+  DeviceGuard() { hipGetDevice(&prev); }
+  ~DeviceGuard() { hipSetDevice(prev); }
+};
+inline int ensure_event(hipEvent_t& e) {  // created at first use, kept (release() destroys it)
+  if (!e) HIPCHK(hipEventCreate(&e), "hipEventCreate");
+  return RTW_OK;
+}
+inline hipStream_t abi_stream(void* s) { return (hipStream_t)s; }  // the C-ABI's `void* stream` (include/rtw.h)
+inline double ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// What a render call renders: the arguments every entry point takes, built once at the extern "C" boundary.
+struct Frame {
+  const rtw_camera* cam;
+  const float* bg;
+  uint32_t w, h, spp, max_depth;
+  uint64_t seed;
+  uint32_t tiles_x() const { return (w + 7u) / 8u; }
+  // 8x8 pixel tiles, ragged edges whole (fits 32 bits for every image the render accepts: sides <= 65536)
+  uint64_t tiles() const { return (uint64_t)((w + 7u) / 8u) * ((h + 7u) / 8u); }
+  uint64_t paths() const { return (uint64_t)w * h * spp; }
+};
 // Which 8x8 tiles a render covers and where they go: slot k renders tile ids[k] (a device array), or
 // tile first + k * stride without one; the output is packed [slot][64][3] when `packed` (always with
 // ids), else the full w x h image.
@@ -155,25 +185,38 @@ struct TileSet {
   uint32_t first = 0, stride = 1, n = 0;
   bool packed = false;
 };
-// enqueue one render (path kernel passes + in-order reductions) on `stream` (hipStream_t) of
-// c.device, which must be current
-int enqueue_render(Scene& s, DeviceCopy& c, const rtw_camera* cam, const float bg[3], uint32_t w, uint32_t h,
-                   uint32_t spp, uint32_t max_depth, uint64_t seed, const TileSet& tiles, float* d_out,
-                   void* stream, uint32_t flags, void* ev0, void* ev1);
+
+// rtw_flatten.cpp
+int flatten(Scene& s);
+// rtw_capi.cpp
+std::string dump_scene(const Scene& s);
+// rtw_render.cpp: the scene's device copies and the render calls' shared opening
+int upload(Scene& s, int device);
+void release(Scene& s);
+DeviceCopy* find_copy(Scene& s, int device);  // device < 0: the first copy
+int grow(DevBuf& b, size_t bytes);            // current device; contents not kept
+// The render calls' argument checks, in this order: a NULL argument (RTW_EINVAL), an uncommitted scene (RTW_ESTATE),
+// an image under 2x2 (RTW_EINVAL).  `out` is the call's image, device pointer or sink.
+int check_frame(const rtw_scene* s, const Frame& f, bool out);
+// find_copy, or NULL with RTW_ENODEV set: "not committed to device <device><hint>", or without a hint (the calls
+// that name no device) "no device copy"
+DeviceCopy* need_copy(Scene& s, int device, const char* hint = "");
+int copy_events(DeviceCopy& c);  // c.ev[0], c.ev[1] exist
 // wait for `stream`, read the launch counters and the ev0 -> ev1 time into st
-int collect_stats(DeviceCopy& c, void* stream, void* ev0, void* ev1, uint64_t paths, rtw_stats* st);
+int collect_stats(DeviceCopy& c, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, uint64_t paths, rtw_stats* st);
 // RTW_EINVAL (and clears it) if a path kernel on c's device tripped its traversal guard since the last check
 int check_guard(DeviceCopy& c);
+float recip_rn(float b);  // RN(1 / b) for an integer-valued b in [1, 2^24) (rtw_diag_recip)
+// rtw_kernel.hip: what needs the device compiler
+// field 0-7 (stack, spill, occ, feat, blk, ncap, half, s16) of the path-kernel configuration the current
+// environment selects for the committed scene (rtw_scene_info 16-23); host only, no device needed
+int64_t selected_kernel_info(const Scene& s, int field);
+// enqueue one render (path kernel passes + in-order reductions) on `stream` of c.device, which must be current;
+// ev0 / ev1 (or NULL) are recorded around it
+int enqueue_render(Scene& s, DeviceCopy& c, const Frame& f, const TileSet& tiles, float* d_out, hipStream_t stream,
+                   uint32_t flags, hipEvent_t ev0, hipEvent_t ev1);
 int enqueue_unpack(uint32_t w, uint32_t h, const uint32_t* d_tiles, uint32_t n_tiles, const float* d_packed,
-                   float* d_image, void* stream);
-
-// thread-local error reporting (rtw_capi.cpp)
-int fail(int code, const char* fmt, ...);
-// A tuning knob's value (RTW_OCC, RTW_BATCH, RTW_LIST_MAX, ...: DESIGN.md §4), or NULL.  The knobs select
-// kernel variants and scheduling parameters for A/B measurements; they are read only when RTW_TUNING=1, so a
-// process that inherits a stray variable still runs the default (measured-best) kernels.  A knob set without
-// the gate is ignored with one warning on stderr (rtw_capi.cpp).
-const char* tuning_env(const char* name);
+                   float* d_image, hipStream_t stream);
 
 }  // namespace rtw
 

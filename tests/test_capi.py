@@ -1,6 +1,7 @@
 """C-ABI checks that need no GPU: the library loads, exports every symbol include/rtw.h
 declares, builder errors match the reference's panics, host-side pieces (camera, tonemap,
 flattener) agree with the oracle.  Nothing here launches a kernel."""
+import ctypes as C
 import re
 from pathlib import Path
 
@@ -188,7 +189,7 @@ def test_bvh4_breadth_first_codes_and_bounds(rtw, name):
 
 def test_camera_reciprocal_is_correctly_rounded(rtw):
     """rtw_render's camera divisions (lib.rs:84-85) use Markstein's correction from the host's
-    RN(1 / (w - 1)) and RN(1 / (h - 1)) (rtw_kernel.hip recip_rn): it must be the IEEE f32 reciprocal
+    RN(1 / (w - 1)) and RN(1 / (h - 1)) (rtw_render.cpp recip_rn): it must be the IEEE f32 reciprocal
     for every image size (w, h <= 65536) and beyond, up to 2^24."""
     b = np.concatenate([np.arange(1, 65536), np.arange(65536, 1 << 24, 4099), [(1 << 24) - 1]]).astype(np.float32)
     got = rtw.diag_recip(b)
@@ -361,3 +362,86 @@ def test_far_bound_pads_sphere_leaves(rtw):
         s.preset(name, aspect, seed=42)
         _commit_anywhere(rtw, s)
         assert s.info(14) == 0, name
+
+
+# ---- the argument checks of the render and status calls: every one of these returns before any HIP call
+RENDER_CALLS = ["rtw_render", "rtw_render_multi", "rtw_render_stream", "rtw_render_device", "rtw_render_device_strided"]
+STATUS_CALLS = ["rtw_diag_corrupt_bvh", "rtw_render_status", "rtw_path_kernel_times"]
+
+
+def _render_call(rtw, name, w=16, h=16, **null):
+    """Call one render entry point on an uncommitted scene with 1 spp, depth 4; null=True arguments (scene, cam, bg,
+    out) are passed as NULL.  `out` is the host image, the device pointer or the pixel sink of that call; none of the
+    calls made here gets as far as touching it (the device pointer is a made-up address)."""
+    L = rtw.lib()
+    scene = rtw.Scene()
+    cam = rtw.Camera.new((0, 0, 5), (0, 0, 0), (0, 1, 0), 40.0, 1.0, 0.0, 5.0)
+    bg = np.zeros(3, np.float32)
+    img = np.zeros((h, w, 3), np.float32)
+    sink = rtw.PIXEL_SINK(lambda px, n, user: 0)
+    s = None if null.get("scene") else scene._p
+    c = None if null.get("cam") else C.byref(cam.c)
+    b = None if null.get("bg") else bg.ctypes.data_as(C.POINTER(C.c_float))
+    no_out = bool(null.get("out"))
+    host = None if no_out else img.ctypes.data_as(C.POINTER(C.c_float))
+    dptr = None if no_out else C.c_void_p(0x1000)
+    frame = (c, b, w, h, 1, 4, 7)  # cam, bg, w, h, spp, max_depth, seed
+    if name == "rtw_render":
+        return L.rtw_render(s, *frame, host, None)
+    if name == "rtw_render_multi":
+        return L.rtw_render_multi(s, 1, *frame, host, None)
+    if name == "rtw_render_stream":
+        return L.rtw_render_stream(s, *frame, 8, rtw.PIXEL_SINK() if no_out else sink, None, None)
+    if name == "rtw_render_device":
+        return L.rtw_render_device(s, 0, *frame, None, 0, dptr, None, 0, None)
+    assert name == "rtw_render_device_strided"
+    return L.rtw_render_device_strided(s, 0, *frame, 0, 1, 1, dptr, None, 0, None)
+
+
+@pytest.mark.parametrize("null", ["scene", "cam", "bg", "out"])
+@pytest.mark.parametrize("name", RENDER_CALLS)
+def test_render_calls_reject_null_arguments(rtw, name, null):
+    assert _render_call(rtw, name, **{null: True}) == rtw.RTW_EINVAL
+
+
+@pytest.mark.parametrize("w", [16, 1])
+@pytest.mark.parametrize("name", RENDER_CALLS)
+def test_render_calls_need_a_committed_scene(rtw, name, w):
+    """RTW_ESTATE also for a 1-pixel-wide image: the state check comes before the size check."""
+    assert _render_call(rtw, name, w=w) == rtw.RTW_ESTATE
+    assert "not committed" in rtw.lib().rtw_last_error().decode()
+
+
+def _status_call(rtw, name, scene_ptr):
+    L = rtw.lib()
+    if name == "rtw_path_kernel_times":
+        return L.rtw_path_kernel_times(scene_ptr, 0, (C.c_float * 4)(), 4)
+    return getattr(L, name)(scene_ptr, 0)
+
+
+@pytest.mark.parametrize("name,code", zip(STATUS_CALLS, ["RTW_ESTATE", "RTW_ENODEV", "RTW_ENODEV"]))
+def test_status_calls_on_an_uncommitted_scene(rtw, name, code):
+    assert _status_call(rtw, name, rtw.Scene()._p) == getattr(rtw, code)
+
+
+@pytest.mark.parametrize("name", STATUS_CALLS)
+def test_status_calls_reject_a_null_scene(rtw, name):
+    assert _status_call(rtw, name, None) == rtw.RTW_EINVAL
+
+
+@pytest.mark.parametrize("first,stride,n", [(0, 0, 1), (4, 1, 1), (0, 1, 5), (2, 2, 2), (0, 0xFFFFFFFF, 2)])
+def test_strided_tile_range_is_checked_first(rtw, first, stride, n):
+    """rtw_render_device_strided on a 16x16 frame (4 tiles): a zero stride, or a last tile first + (n - 1) * stride at
+    or beyond the frame's tile count, is RTW_EINVAL before the scene's state is looked at (the scene here is
+    uncommitted: a call whose range fits returns RTW_ESTATE)."""
+    L = rtw.lib()
+    s = rtw.Scene()
+    cam = rtw.Camera.new((0, 0, 5), (0, 0, 0), (0, 1, 0), 40.0, 1.0, 0.0, 5.0)
+    bg = np.zeros(3, np.float32)
+    frame = (C.byref(cam.c), bg.ctypes.data_as(C.POINTER(C.c_float)), 16, 16, 1, 4, 7)
+
+    def call(first, stride, n):
+        return L.rtw_render_device_strided(s._p, 0, *frame, first, stride, n, C.c_void_p(0x1000), None, 0, None)
+    assert call(first, stride, n) == rtw.RTW_EINVAL
+    assert "leave the frame's 4 tiles" in rtw.lib().rtw_last_error().decode()
+    assert call(3, 1, 1) == call(1, 2, 2) == call(0, 1, 4) == rtw.RTW_ESTATE

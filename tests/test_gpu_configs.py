@@ -5,6 +5,7 @@ scenes.rs:63-162).  The whole frame is rendered through rtw_render and compared 
 its ray count, against the oracle; rtw_console (the console_app mirror) is run at that config and its
 PNG is checked against rtw_tonemap of the GPU sums (main.rs:68-94).
 """
+import ctypes as C
 import os
 import subprocess
 from pathlib import Path
@@ -222,3 +223,93 @@ def test_strided_tiles_match_full_frame(gpu):
         torch.cuda.synchronize()
         assert rays == st["rays"], world
         assert np.array_equal(img.cpu().numpy().view(np.uint32), full.view(np.uint32)), world
+
+
+# ---- the argument checks of the render calls on a committed scene (tests/test_capi.py has those that need no device)
+FRAME = (16, 16, 1, 4)  # w, h, spp, max_depth
+LOOK_FROM = (0, 0.6, 3)
+
+
+@pytest.fixture(scope="module")
+def small_world(gpu):
+    """Three spheres in a BVH plus one moving sphere, committed to device 0 with the motion range [0, 1], and its
+    16x16 frame through rtw_render, rendered once: (rtw, scene, camera, background, frame, rays)."""
+    rtw = gpu
+    s = rtw.Scene()
+    m = s.lambertian_solid((0.5, 0.6, 0.7))
+    with s.bvh(0.0, 1.0):
+        s.spheres([(-1.2, 0, 0), (0, 0, 0), (1.2, 0, 0)], [0.5, 0.5, 0.5], [m, m, m])
+    s.moving_sphere((0, 1.0, 0), 0.0, (0, 1.4, 0), 1.0, 0.3, m)
+    s.commit(device=0)
+    cam = rtw.Camera.new(LOOK_FROM, (0, 0.4, 0), (0, 1, 0), 50.0, 1.0, 0.0, 3.0, 0.0, 1.0)
+    bg = (0.7, 0.8, 1.0)
+    w, h, spp, depth = FRAME
+    ref, st = rtw.Raytracer(s, cam, bg, w, h, spp, seed=11, max_depth=depth).render()
+    assert st["rays"] > w * h * spp and np.isfinite(ref).all()  # some paths hit a sphere and bounce
+    ref.setflags(write=False)
+    return rtw, s, cam, bg, ref, st["rays"]
+
+
+def test_rejected_render_calls_leave_nothing_behind(small_world):
+    """A render call with a 1-pixel-wide image, a device the scene was not committed to, a shutter outside the
+    committed motion range or a side over 65536 returns its error code on the host, before any launch: the output
+    keeps its fill, no path-kernel launch is recorded, and the next frame equals the first bit for bit with a clean
+    rtw_render_status."""
+    torch = pytest.importorskip("torch")
+    rtw, s, cam, bg, ref, rays = small_world
+    w, h, spp, depth = FRAME
+    s.path_kernel_times(0)  # forget the launches so far
+    stream = torch.cuda.current_stream().cuda_stream
+    wide = rtw.Camera.new(LOOK_FROM, (0, 0.4, 0), (0, 1, 0), 50.0, 1.0, 0.0, 3.0, 0.0, 2.0)  # shutter [0, 2)
+
+    def host(cam_, w_, h_):
+        rt = rtw.Raytracer(s, cam_, bg, w_, h_, spp, seed=11, max_depth=depth)
+        out = np.full((h_, w_, 3), -7.0, np.float32)
+        st = rtw.rtw_stats()
+        rc = rtw.lib().rtw_render(s._p, C.byref(cam_.c), rtw._fp(rt.bg), w_, h_, spp, depth, 11,
+                                  out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(st))
+        assert (out == -7.0).all() and st.rays == 0
+        return rc
+
+    def device(dev, w_, h_):
+        out = torch.full((h_, w_, 3), -7.0, dtype=torch.float32, device="cuda:0")
+        with pytest.raises(rtw.RtwError) as e:
+            rtw.Raytracer(s, cam, bg, w_, h_, spp, seed=11, max_depth=depth).render_device(
+                out.data_ptr(), dev, 0, 0, stream, want_stats=True)
+        torch.cuda.synchronize()
+        assert bool((out == -7.0).all())
+        return e.value.code
+
+    assert host(cam, 1, h) == rtw.RTW_EINVAL
+    assert "at least 2x2" in rtw.lib().rtw_last_error().decode()
+    assert device(0, 1, h) == rtw.RTW_EINVAL
+    assert device(5, w, h) == rtw.RTW_ENODEV
+    assert "not committed to device 5" in rtw.lib().rtw_last_error().decode()
+    assert host(wide, w, h) == rtw.RTW_EINVAL
+    assert "outside the committed motion range" in rtw.lib().rtw_last_error().decode()
+    assert host(cam, 65537, 2) == rtw.RTW_EINVAL
+    assert "at most 65536" in rtw.lib().rtw_last_error().decode()
+    assert s.path_kernel_times(0) == []  # nothing was launched
+    again, st = rtw.Raytracer(s, cam, bg, w, h, spp, seed=11, max_depth=depth).render()
+    assert st["rays"] == rays
+    assert np.array_equal(again.view(np.uint32), ref.view(np.uint32))
+    s.render_status(0)
+
+
+def test_entry_points_render_the_same_frame(small_world):
+    """rtw_render, rtw_render_device with stats and rtw_render_stream (8-row bands) give the same 16x16 frame bit for
+    bit and count the same rays."""
+    torch = pytest.importorskip("torch")
+    rtw, s, cam, bg, ref, rays = small_world
+    w, h, spp, depth = FRAME
+    rt = rtw.Raytracer(s, cam, bg, w, h, spp, seed=11, max_depth=depth)
+    out = torch.zeros((h, w, 3), dtype=torch.float32, device="cuda:0")
+    st = rt.render_device(out.data_ptr(), 0, 0, 0, torch.cuda.current_stream().cuda_stream, want_stats=True)
+    assert st["rays"] == rays and st["paths"] == w * h * spp
+    assert np.array_equal(out.cpu().numpy().view(np.uint32), ref.view(np.uint32))
+    bands = []
+    st = rt.render_stream(bands.append, band_rows=8)
+    px = np.concatenate(bands)
+    assert len(bands) == 2 and st["rays"] == rays and st["paths"] == w * h * spp
+    assert np.array_equal(px["row"], np.repeat(np.arange(h - 1, -1, -1), w))
+    assert np.array_equal(px["color"].reshape(h, w, 3).view(np.uint32), ref.view(np.uint32))
