@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define RTW_ABI_VERSION 6
+#define RTW_ABI_VERSION 7
 
 enum {
   RTW_OK = 0,
@@ -219,7 +219,8 @@ int rtw_progress_decode(const uint8_t* frame, size_t len, rtw_progress_msg* msg)
  * are left untouched).  `stream` is a hipStream_t (NULL = default).  The call only enqueues unless
  * stats != NULL, in which case it synchronises and fills stats.  Each (scene, device) pair owns one
  * path queue and one sample buffer: renders of a scene on one device must be serialised on one
- * stream (two renders in flight on different streams would share them).  The first render of a
+ * stream (two renders in flight on different streams would share them); so must its ray queries
+ * (rtw_hit_rays*), which share the traversal-stack spill area with them.  The first render of a
  * given size allocates the sample buffer (hipMalloc: not stream-capturable); later renders of the
  * same or a smaller size only enqueue.  Without stats, a traversal fault of this render surfaces at
  * the first rtw_render* call that starts after this render has COMPLETED (the check reads the device's
@@ -236,6 +237,51 @@ int rtw_render_device_strided(rtw_scene* s, int device, const rtw_camera* cam, c
                               uint32_t w, uint32_t h, uint32_t spp, uint32_t max_depth, uint64_t seed,
                               uint32_t first_tile, uint32_t tile_stride, uint32_t n_tiles, float* d_out,
                               void* stream, uint32_t flags, rtw_stats* stats);
+/* ---- closest-hit ray queries: Hittable::hit(&ray, t_min, t_max) -> Option<HitRecord> on the world list
+ *      (hittable/mod.rs:22-69) for rays the caller chooses.  A query is world.hit(ray, 0.001, +inf), the interval of
+ *      lib.rs:102 and the only one the render's culling is proven for: t_min and t_max are not parameters.  The winner
+ *      is the render's winner (ties go to the later object; BvhNode groups are sets), found by the path
+ *      kernel's own walk for this scene. */
+/* ray.rs Ray.  stream: the path RNG state at the segment start, which keys ConstantMedium's free-path sub-stream
+ * (rtw_begin_constant_medium); irrelevant for worlds without media.  reserved: 0. */
+typedef struct {
+  float origin[3], direction[3];
+  float time;
+  uint32_t reserved;
+  uint64_t stream;
+} rtw_ray;
+/* hittable/mod.rs:22-29 HitRecord.  material: the id the rtw_material_* / rtw_begin_constant_medium call returned.
+ * key: the winning leaf's depth-first number in the committed hierarchy, the order rtw_scene_dump lists leaves (a
+ * Cuboid counts as its six sides, in rectangular.rs:177-240's order xy, xy, xz, xz, yz, yz; a mesh or
+ * rtw_add_triangles call as one leaf per triangle, in input order; a ConstantMedium as one leaf, its boundary not
+ * counted).  A miss has flags = 0, t = +inf and zeros elsewhere. */
+typedef struct {
+  float p[3], normal[3];
+  float t, u, v;
+  uint32_t material, key, flags;
+} rtw_hit;
+enum {
+  RTW_HIT_HIT = 1,        /* the ray hit: the other fields are the HitRecord */
+  RTW_HIT_FRONT_FACE = 2, /* HitRecord::front_face */
+  RTW_HIT_BAD_RAY = 4     /* time is NaN or outside the committed motion range: not traced (a miss record) */
+};
+/* n rays from host memory, blocking: `rays` is rtw_ray[n], `hits` receives rtw_hit[n] (typed void* as `stream` is;
+ * the typed forms are in the mirrors).  Rays and records are staged through device buffers the scene's device copy
+ * keeps (grown once), at most 2^20 rays at a time, so n is unbounded.  device -1 = the first copy.  RTW_EINVAL: a NULL
+ * argument with n > 0, or a ray whose time is NaN or outside the motion range the scene's moving spheres were committed
+ * with (found by a host scan before anything is enqueued), or a traversal guard trip (rtw_render_status); RTW_ESTATE:
+ * the scene was never flattened by rtw_scene_commit; RTW_ENODEV: no device copy.  n = 0 is RTW_OK and touches no device.
+ * Degenerate rays (zero, infinite or NaN components) are legal: the walk is bounded, their records are what the
+ * render's arithmetic gives, and their neighbours' records are unaffected.  stats (may be NULL): rays = n, paths = 0,
+ * kernel_ms, total_ms; the traversal counters stay 0. */
+int rtw_hit_rays(rtw_scene* s, int device, uint64_t n, const void* rays, void* hits, rtw_stats* stats);
+/* The same from DEVICE arrays (16-byte aligned) on the caller's `stream`.  It only enqueues unless stats != NULL, as
+ * rtw_render_device; a pending guard trip is reported before it enqueues.  No host scan: a ray with a bad time comes
+ * back with RTW_HIT_BAD_RAY.  A query uses the device copy's traversal-stack spill area, so queries and renders of one
+ * (scene, device) must be serialised on one stream, as renders among themselves (rtw_render_device). */
+int rtw_hit_rays_device(rtw_scene* s, int device, uint64_t n, const void* d_rays, void* d_hits, void* stream,
+                        rtw_stats* stats);
+
 /* Errors of renders the caller did not wait for.  A path kernel whose BVH walk trips its guard (a
  * corrupt tree: the walk is bounded, and the first trip closes the path queue, so the grid drains after
  * about one trip per wave) sets the device's host-mapped error word.  It is reported, and cleared, as

@@ -77,6 +77,21 @@ class rtw_progress_msg(C.Structure):  # lib.rs:128-138 ProgressMessage
                 ("samples_per_pixel", C.c_uint32), ("pixel", rtw_pixel)]
 
 
+class rtw_ray(C.Structure):  # ray.rs Ray + the segment's stream word (include/rtw.h)
+    _fields_ = [("origin", C.c_float * 3), ("direction", C.c_float * 3), ("time", C.c_float),
+                ("reserved", C.c_uint32), ("stream", C.c_uint64)]
+
+
+class rtw_hit(C.Structure):  # hittable/mod.rs:22-29 HitRecord
+    _fields_ = [("p", C.c_float * 3), ("normal", C.c_float * 3), ("t", C.c_float), ("u", C.c_float),
+                ("v", C.c_float), ("material", C.c_uint32), ("key", C.c_uint32), ("flags", C.c_uint32)]
+
+
+HIT_HIT, HIT_FRONT_FACE, HIT_BAD_RAY = 1, 2, 4
+RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("direction", np.float32, 3), ("time", np.float32),
+                      ("reserved", np.uint32), ("stream", np.uint64)])
+HIT_DTYPE = np.dtype([("p", np.float32, 3), ("normal", np.float32, 3), ("t", np.float32), ("u", np.float32),
+                      ("v", np.float32), ("material", np.uint32), ("key", np.uint32), ("flags", np.uint32)])
 MSG_IMAGE_START, MSG_PIXEL, MSG_IMAGE_END = 0, 1, 2
 PIXEL_SINK = C.CFUNCTYPE(C.c_int, C.POINTER(rtw_pixel), C.c_uint32, C.c_void_p)
 PIXEL_DTYPE = np.dtype([("row", np.uint32), ("column", np.uint32), ("color", np.float32, 3)])
@@ -124,6 +139,10 @@ _SIGS = {
     "rtw_render_device_strided": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(rtw_camera), _F, C.c_uint32,
                                             C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32,
                                             C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(rtw_stats)]),
+    "rtw_hit_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(rtw_ray), C.POINTER(rtw_hit),
+                               C.POINTER(rtw_stats)]),
+    "rtw_hit_rays_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.POINTER(rtw_stats)]),
     "rtw_render_status": (C.c_int, [C.c_void_p, C.c_int]),
     "rtw_diag_corrupt_bvh": (C.c_int, [C.c_void_p, C.c_int]),
     "rtw_diag_alias_devices": (C.c_int, [C.c_void_p, C.c_int]),
@@ -158,7 +177,7 @@ EXPORTED_SYMBOLS = tuple(_SIGS)
 _lib = None
 
 
-ABI_VERSION = 6  # include/rtw.h RTW_ABI_VERSION
+ABI_VERSION = 7  # include/rtw.h RTW_ABI_VERSION
 
 
 def lib_sha() -> str:
@@ -422,6 +441,26 @@ class Scene:
             _check(n)
         return [float(buf[q]) for q in range(min(n, max_n))], float(g.value)
 
+    def hit_rays(self, origins, directions, times=None, streams=None, device: int = -1, want_stats: bool = False):
+        """world.hit(ray, 0.001, inf) (hittable/mod.rs:57-69) for n rays: origins and directions [n, 3], times [n]
+        (default 0) and the segments' stream words [n] (default 0; they key a ConstantMedium's free path).
+        -> records as a structured array of HIT_DTYPE (rtw_hit's layout)[, stats]."""
+        rays = make_rays(origins, directions, times, streams)
+        hits = np.zeros(len(rays), HIT_DTYPE)
+        st = rtw_stats()
+        _check(lib().rtw_hit_rays(self._p, device, len(rays), rays.ctypes.data_as(C.POINTER(rtw_ray)),
+                                  hits.ctypes.data_as(C.POINTER(rtw_hit)), C.byref(st)))
+        return (hits, st.as_dict()) if want_stats else hits
+
+    def hit_rays_device(self, d_rays_ptr: int, d_hits_ptr: int, n: int, device: int = 0, stream_ptr: int = 0,
+                        want_stats: bool = False):
+        """Enqueue the query of n rays in device memory (rtw_ray[n] -> rtw_hit[n], both 16-byte aligned) on a
+        stream; waits only for stats."""
+        st = rtw_stats()
+        _check(lib().rtw_hit_rays_device(self._p, device, n, C.c_void_p(d_rays_ptr), C.c_void_p(d_hits_ptr),
+                                         C.c_void_p(stream_ptr), C.byref(st) if want_stats else None))
+        return st.as_dict() if want_stats else None
+
     def render_status(self, device: int = -1) -> None:
         """Wait for the device and raise if a render since the last check tripped the traversal guard."""
         _check(lib().rtw_render_status(self._p, device))
@@ -537,6 +576,19 @@ class Raytracer:
             self.seed, first_tile, tile_stride, n_tiles, C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr), flags,
             C.byref(st) if want_stats else None))
         return st.as_dict() if want_stats else None
+
+
+def make_rays(origins, directions, times=None, streams=None) -> np.ndarray:
+    """rtw_ray records (RAY_DTYPE) from [n, 3] origins and directions, times [n] and stream words [n]."""
+    o = np.asarray(origins, np.float32).reshape(-1, 3)
+    rays = np.zeros(len(o), RAY_DTYPE)
+    rays["origin"] = o
+    rays["direction"] = np.asarray(directions, np.float32).reshape(-1, 3)
+    if times is not None:
+        rays["time"] = np.asarray(times, np.float32).reshape(-1)
+    if streams is not None:
+        rays["stream"] = np.asarray(streams, np.uint64).reshape(-1)
+    return rays
 
 
 def progress_encode(kind: int, width=0, height=0, spp=0, pixel=None) -> bytes:

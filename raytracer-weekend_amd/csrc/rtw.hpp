@@ -12,6 +12,7 @@
 //   BvhNode::new(objs, t0, t1, rng)                     world.bvh(t0, t1, [&]{ ... })
 //   load_wavefront_obj(path, rng)                       world.load_wavefront_obj(path)
 //   Raytracer::new(..).render() -> Pixel stream         Raytracer(..).render() -> std::vector<Pixel>
+//   world.hit(&ray, 0.001, INFINITY) -> Option<HitRecord>  world.hit_rays(rays) -> std::vector<Hit>  hittable/mod.rs:22-69
 // Errors (the reference panics) throw rtw::Error with rtw_last_error()'s message.
 #pragma once
 #include <stdexcept>
@@ -42,6 +43,29 @@ struct Pixel {
   Color color;
 };
 
+using TextureId = uint32_t;
+using MaterialId = uint32_t;
+
+// ray.rs Ray (+ the segment's stream word, which keys a ConstantMedium's free path) and hittable/mod.rs:22-29
+// HitRecord, laid out as the C-ABI's rtw_ray / rtw_hit
+struct Ray {
+  Point3 origin;
+  Vec3 direction;
+  float time = 0.f;
+  uint32_t reserved = 0;
+  uint64_t stream = 0;
+};
+struct Hit {
+  Point3 p;
+  Vec3 normal;
+  float t, u, v;
+  MaterialId material;
+  uint32_t key, flags;
+  bool hit() const { return flags & RTW_HIT_HIT; }
+  bool front_face() const { return flags & RTW_HIT_FRONT_FACE; }
+};
+static_assert(sizeof(Ray) == sizeof(rtw_ray) && sizeof(Hit) == sizeof(rtw_hit), "rtw::Ray / rtw::Hit mirror rtw.h");
+
 struct Camera {
   rtw_camera c{};
   static Camera new_(Point3 from, Point3 at, Vec3 up, float vfov, float aspect, float aperture, float focus,
@@ -52,9 +76,6 @@ struct Camera {
     return k;
   }
 };
-
-using TextureId = uint32_t;
-using MaterialId = uint32_t;
 
 class World {
  public:
@@ -134,6 +155,12 @@ class World {
     return out;
   }
   void commit(int device = -1) { check(rtw_scene_commit(s_, device)); }
+  // [Box<dyn Hittable>]::hit(&ray, 0.001, INFINITY) for every ray (hittable/mod.rs:57-69), on the GPU; blocking
+  std::vector<Hit> hit_rays(const std::vector<Ray>& rays, int device = -1, rtw_stats* st = nullptr) const {
+    std::vector<Hit> hits(rays.size());
+    check(rtw_hit_rays(s_, device, rays.size(), rays.data(), hits.data(), st));
+    return hits;
+  }
 
  private:
   rtw_scene* s_ = nullptr;

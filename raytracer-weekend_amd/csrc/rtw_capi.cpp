@@ -398,7 +398,9 @@ int rtw_scene_commit(rtw_scene* s, int device) {
   if (!s) return fail(RTW_EINVAL, "scene is NULL");
   if (s->s.committed) return fail(RTW_ESTATE, "scene already committed");
   if (s->s.open.size() != 1) return fail(RTW_ESTATE, "%zu group(s) still open", s->s.open.size() - 1);
+  s->s.flattened = false;
   if (int e = flatten(s->s)) return e;
+  s->s.flattened = true;
   if (int e = upload(s->s, device)) return e;
   s->s.committed = true;
   return RTW_OK;

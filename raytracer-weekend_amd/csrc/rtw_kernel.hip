@@ -1,9 +1,9 @@
 // rtw_kernel.hip — what of the gfx950 path-tracing megakernel's host side needs the device compiler: the kernels
 // that are no templates (reduce_kernel, unpack_tiles_kernel, the libm and reciprocal diagnostics, with the two calls
 // that launch the latter), the tuning knobs, pick_kernel (which path-kernel variant a scene runs) and the launches
-// (enqueue_render, enqueue_unpack).  The scene's device copies, statistics and the render entry points are plain HIP
-// runtime code in rtw_render.cpp.  The device code is in headers that this unit and rtw_kernel_mesh.hip (the F_MESHES
-// variants, under their own compiler flags) both include.
+// (enqueue_render, enqueue_hit_rays, enqueue_unpack).  The scene's device copies, statistics and the render and
+// ray-query entry points are plain HIP runtime code in rtw_render.cpp.  The device code is in headers that this unit
+// and rtw_kernel_mesh.hip (the F_MESHES variants, under their own compiler flags) both include.
 //
 // Hot path restated (reference raytracer_weekend_lib/src/):
 //   Raytracer::render / sample_pixel (lib.rs:57-95)   -> one work unit per path (pixel, sample); the samples
@@ -32,6 +32,8 @@
 // loops: regenerate -> trace_begin (the always-tested list) -> trace_run (resumable BVH4 walk with
 // postponed leaves; returns once quota16/16 of the lanes are done) -> shade.  A finished path writes
 // its radiance to an ordered sample buffer that reduce_kernel sums per pixel in sample order.
+// Ray queries (rtw_hit_rays*): hit_kernel<K> (rtw_query_kernel.hpp) runs caller rays through the same trace_begin /
+// trace_run / hit_record under the scene's own K, one ray per lane, grid-stride; instantiated beside path_kernel<.., K>.
 // Variants: path_kernel<COUNT, KernelCfg K> -- one plain aggregate (stack rows, spill, waves / SIMD, feature set,
 // workgroup size, LDS node table, half nodes, 16-bit stack) is the template argument, defines every property derived
 // from it, and travels with the kernel to the host (Variant, rtw_variants.hpp), which sizes the launch from it.
@@ -439,6 +441,51 @@ int enqueue_render(Scene& sc, DeviceCopy& c, const Frame& f, const TileSet& ts, 
     HIPCHK(hipMemsetAsync(d_out, 0, n * sizeof(float), stream), "hipMemsetAsync(out)");
   } else if (ts.n) {
     if (int e = run_passes(sc, c, a, kn, ts.n, flags & RTW_FLAG_COUNT_TRAVERSAL, stream)) return e;
+  }
+  if (ev1) HIPCHK(hipEventRecord(ev1, stream), "hipEventRecord");
+  return RTW_OK;
+}
+
+// Ray queries (rtw_hit_rays*): the scene's variant as its renders pick it, the query kernel's own resident capacity
+// as the largest grid, and the walk's launch tuning (leaf16, the spill split) from tune_launch.
+int enqueue_hit_rays(Scene& sc, DeviceCopy& c, uint64_t n, const void* d_rays, void* d_hits, hipStream_t stream,
+                     hipEvent_t ev0, hipEvent_t ev1) {
+  const Knobs kn = read_knobs();
+  const Variant var = path_kernel_variant(sc.flat, kn);
+  const KernelCfg& k = var.cfg;
+  if (c.hit_grid <= 0 || c.hit_grid_fn != (const void*)var.hit) {
+    int per_cu = 0, cus = 0;
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, var.hit, k.blk, 0);
+    if (e != hipSuccess || per_cu < 1) per_cu = 1;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.phys) != hipSuccess || cus < 1) cus = 256;
+    c.hit_grid = per_cu * cus;
+    c.hit_grid_fn = (const void*)var.hit;
+    if (kn.verbose)
+      fprintf(stderr, "rtw: query kernel %p: block %d, %d resident blocks per CU x %d CUs\n", (void*)var.hit, k.blk,
+              per_cu, cus);
+  }
+  RenderArgs t;
+  memset(&t, 0, sizeof t);
+  tune_launch(t, kn, sc.flat, k, c.hit_grid);
+  if (int e = grow(c.spill, (size_t)t.spill_depth * t.spill_lanes * sizeof(int32_t))) return e;
+  QueryArgs a;
+  memset(&a, 0, sizeof a);
+  a.scene = c.scene;
+  a.rays = d_rays;
+  a.hits = d_hits;
+  a.n = n;
+  a.time_lo = sc.flat.time_lo;
+  a.time_hi = sc.flat.time_hi;
+  a.leaf16 = t.leaf16;
+  a.spill_lanes = t.spill_lanes;
+  a.spill = static_cast<int32_t*>(c.spill.p);
+  a.err = c.err_host;
+  const uint64_t blocks = (n + (uint32_t)k.blk - 1u) / (uint32_t)k.blk;
+  const int grid = (int)std::min<uint64_t>((uint64_t)c.hit_grid, blocks);
+  if (ev0) HIPCHK(hipEventRecord(ev0, stream), "hipEventRecord");
+  if (grid > 0) {
+    hipLaunchKernelGGL(var.hit, dim3(grid), dim3(k.blk), 0, stream, a);
+    HIPCHK(hipGetLastError(), "hit_kernel launch");
   }
   if (ev1) HIPCHK(hipEventRecord(ev1, stream), "hipEventRecord");
   return RTW_OK;

@@ -1,0 +1,123 @@
+// rtw_query_kernel.hpp — closest-hit ray queries: Hittable::hit on the world list (hittable/mod.rs:22-69) for rays
+// the caller chooses, instead of the camera paths of path_kernel.  hit_kernel<KernelCfg K> is instantiated beside
+// path_kernel<COUNT, K> (make_variant, rtw_variants.hpp), so a scene's queries run the walk and feature set its
+// renders run: the list loops, the 32-bit, 16-bit (S16), half-node and LDS-node walks, the HBM stack spill, trace_far.
+//
+// A query is world.hit(ray, 0.001, +inf): lib.rs:102's interval, the only one the culling pads, the far bound and the
+// list loops' NaN rule are proven for.  Caller-chosen t_min / t_max are not offered.  The winner is the render's: ties
+// to the later object, BvhNode groups as sets, the in-plane (NaN) hit reported by the list-mode loops only
+// (DESIGN.md §2).  rtw_ray::stream is the segment word that keys ConstantMedium's free-path sub-stream.
+//
+// What it shares with path_kernel: the LDS stack columns and node table of K, trace_begin, trace_run, hit_record.
+// What it leaves out: the path queue, id pool and start ring, StartArgs, shading, the sample buffer, COUNT builds.
+#pragma once
+#include "../../include/rtw.h"
+#include "rtw_path_kernel.hpp"
+
+namespace rtw {
+
+struct QueryArgs {
+  DevScene scene;
+  const void* rays;      // rtw_ray[n], 16-byte aligned
+  void* hits;            // rtw_hit[n], 16-byte aligned
+  uint64_t n;
+  float time_lo, time_hi;  // the committed motion range (Flat): a ray outside it is not traced (RTW_HIT_BAD_RAY)
+  uint32_t leaf16;       // RenderArgs::leaf16
+  uint32_t spill_lanes;  // RenderArgs::spill_lanes
+  int32_t* spill;        // RenderArgs::spill
+  uint32_t* err;         // RenderArgs::err
+};
+
+namespace dev {
+
+static_assert(sizeof(rtw_ray) == 40 && sizeof(rtw_hit) == 48, "rtw_ray / rtw_hit layout (include/rtw.h)");
+// a ray record starts on an 8-byte boundary (40 B each): its two 16-byte quads and the stream word
+typedef float ray_quad __attribute__((ext_vector_type(4), aligned(8)));
+typedef uint32_t ray_pair __attribute__((ext_vector_type(2), aligned(8)));
+
+// Each lane owns one ray and a wave takes 64 consecutive ones (the caller's order decides coherence); grid-stride
+// over n, the grid at most the resident capacity, so an LDS-node workgroup copies its node table once.  The last
+// wave runs partial under its exec mask.
+template <KernelCfg K>
+__global__ __launch_bounds__(K.blk) __attribute__((amdgpu_waves_per_eu(K.occ, 8))) void hit_kernel(QueryArgs a) {
+  // path_kernel's LDS without the LST rows: the stack columns (+ 1: trace_run's branch-free push) and the node table
+  __shared__ int32_t stk_all[K.codes16_stack() ? 1 : (K.stack + 1) * K.blk];
+  __shared__ uint16_t stk16_all[K.ncap > 0 ? K.stack * K.blk : (K.s16 ? (K.stack + 1) * K.blk : 1)];
+  __shared__ float4 nodes_lds[K.ncap > 0 ? K.ncap * K.node_quads()
+                                         : (K.root_lds() ? RTW_MESH_ROOT * K.node_quads() : 1)];
+  if constexpr (K.ncap > 0) {  // the host launches this variant only when Flat::codes16 and n_nodes <= NCAP
+    const float4* g = K.half ? reinterpret_cast<const float4*>(a.scene.hnodes)
+                             : reinterpret_cast<const float4*>(a.scene.nodes);
+    for (uint32_t k = threadIdx.x; k < a.scene.n_nodes * K.node_quads(); k += K.blk) nodes_lds[k] = g[k];
+  }
+  if constexpr (K.root_lds()) {
+    const uint32_t nq = min(a.scene.n_nodes, (uint32_t)RTW_MESH_ROOT) * K.node_quads();
+    if (threadIdx.x < nq) nodes_lds[threadIdx.x] = reinterpret_cast<const float4*>(a.scene.hnodes)[threadIdx.x];
+  }
+  __syncthreads();
+  uint16_t* stk16 = stk16_all + threadIdx.x;
+  int32_t* stk = stk_all + threadIdx.x;
+  int32_t* spill = a.spill + (size_t)blockIdx.x * K.blk + threadIdx.x;  // unused unless the variant spills
+  const DevScene& S = a.scene;
+  uint32_t cnt[15] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // (COUNT builds only: never touched here)
+  uint64_t ph[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  const uint64_t stride = (uint64_t)gridDim.x * K.blk;
+  // wave-uniform: the wave's first ray
+  for (uint64_t base = (uint64_t)blockIdx.x * K.blk + (threadIdx.x & ~63u); base < a.n; base += stride) {
+    const uint64_t i = base + (threadIdx.x & 63u);
+    bool tripped = false;
+    if (i < a.n) {
+      const char* rp = reinterpret_cast<const char*>(a.rays) + i * sizeof(rtw_ray);
+      const ray_quad r0 = *reinterpret_cast<const ray_quad*>(rp);       // origin, direction.x
+      const ray_quad r1 = *reinterpret_cast<const ray_quad*>(rp + 16);  // direction.y, .z, time, reserved
+      const ray_pair r2 = *reinterpret_cast<const ray_pair*>(rp + 32);  // stream
+      Ray ray;
+      ray.o = mk(r0.x, r0.y, r0.z);
+      ray.d = mk(r0.w, r1.x, r1.y);
+      ray.time = r1.z;
+      const uint64_t seg = ((uint64_t)r2.y << 32) | r2.x;
+      // the BVH's moving-sphere boxes bound [time_lo, time_hi] only: a NaN time fails both compares
+      const bool bad = !(ray.time >= a.time_lo && ray.time <= a.time_hi);
+      float4 o0 = make_float4(0.f, 0.f, 0.f, 0.f), o1 = make_float4(0.f, 0.f, INFINITY, 0.f);
+      uint32_t mat = 0u, key = 0u, flags = bad ? (uint32_t)RTW_HIT_BAD_RAY : 0u;
+      float v = 0.f;
+      if (!bad) {
+        TraceState ts;
+        trace_begin<false, K.feat, K.stack, K.blk, K.codes16_stack(), K.far_lds_nodes()>(S, ray, ts, cnt, seg, stk16, stk,
+                                                                                         a.err, nodes_lds);
+        if constexpr (!(K.feat & F_LIST)) {
+          // quota = every active lane: trace_run returns when all of them are done (or its guard tripped)
+          do {
+            const uint32_t act = (uint32_t)__popcll(__ballot(1));
+            const uint32_t leaf_thr = (act * a.leaf16 + 15u) >> 4;
+            trace_run<false, K.stack, K.spill, K.feat, K.blk, K.ncap, K.half, K.s16>(
+                S, ray, ts, stk, spill, a.spill_lanes, cnt, act, leaf_thr, seg, a.err, ph + 4, nodes_lds, stk16);
+          } while (ts.node >= 0 || ts.sp > 0);
+          __builtin_amdgcn_s_setprio(0);  // trace_run raised it
+        }  // (list mode: trace_begin tested every primitive)
+        const Best b = ts.b;
+        tripped = b.prim == -2;  // trace_run / trace_far wrote the sticky error word
+        if (b.prim >= 0) {
+          // the whole HitRecord, the sphere's uv included (spherical.rs:62-77 computes it for every hit)
+          const Rec h = hit_record<K.feat | F_UV>(S, ray, b, 1u << 12);
+          o0 = make_float4(h.p.x, h.p.y, h.p.z, h.n.x);
+          o1 = make_float4(h.n.y, h.n.z, b.t, h.u);
+          v = h.v;
+          mat = h.mat;
+          key = S.prims[b.prim].key;
+          flags = (uint32_t)RTW_HIT_HIT | (h.front ? (uint32_t)RTW_HIT_FRONT_FACE : 0u);
+        }
+      }
+      float4* hp = reinterpret_cast<float4*>(reinterpret_cast<char*>(a.hits) + i * sizeof(rtw_hit));
+      hp[0] = o0;
+      hp[1] = o1;
+      hp[2] = make_float4(v, __uint_as_float(mat), __uint_as_float(key), __uint_as_float(flags));
+    }
+    // a corrupt tree (the call reports RTW_EINVAL and its records are invalid): the wave stops after its first trip,
+    // 2^20 node-loop iterations, so the grid drains after one trip per wave
+    if (__any(tripped)) break;
+  }
+}
+
+}  // namespace dev
+}  // namespace rtw

@@ -1,8 +1,8 @@
 // rtw_render.cpp — the host render runtime behind the C-ABI's device half: the scene's device copies (upload, release,
 // the grow-only buffers), the render calls' shared opening (check_frame, need_copy), statistics, the traversal guard's
-// error word, and the render / status entry points of one device.  Plain HIP runtime API: the kernels, which variant a
-// scene runs and how a render is enqueued are rtw_kernel.hip's (enqueue_render, enqueue_unpack); the render over
-// several devices is rtw_multi.cpp's.
+// error word, and the render / ray-query / status entry points of one device.  Plain HIP runtime API: the kernels, which
+// variant a scene runs and how a render or a query is enqueued are rtw_kernel.hip's (enqueue_render, enqueue_hit_rays,
+// enqueue_unpack); the render over several devices is rtw_multi.cpp's.
 #include <math.h>
 #include <string.h>
 
@@ -104,7 +104,8 @@ void release(Scene& s) {
     if (c.block) hipFree(c.block);
     if (c.counters) hipFree(c.counters);
     if (c.err_host) hipHostFree(c.err_host);
-    for (DevBuf* b : {&c.sbuf, &c.spill, &c.image, &c.tiles, &c.packed, &c.gathered, &c.gather_ids}) free_buf(*b);
+    for (DevBuf* b : {&c.sbuf, &c.spill, &c.image, &c.tiles, &c.packed, &c.gathered, &c.gather_ids, &c.qrays, &c.qhits})
+      free_buf(*b);
     for (hipEvent_t e : {c.ev[0], c.ev[1], c.gev[0], c.gev[1]})
       if (e) hipEventDestroy(e);
     if (c.stream) hipStreamDestroy(c.stream);
@@ -268,6 +269,88 @@ int rtw_render_device_strided(rtw_scene* s, int device, const rtw_camera* cam, c
                 (unsigned long long)nt);
   const TileSet ts{nullptr, first_tile, tile_stride, n_tiles, true};
   return render_device(s, device, f, ts, d_out, abi_stream(stream), flags, stats);
+}
+
+// rtw_hit_rays and rtw_hit_rays_device: the checks they share, in the render calls' order (a NULL argument, then the
+// scene's state).  The state asked for is a flattened scene, so that a commit that found no device answers RTW_ENODEV.
+static int hit_rays_check(const rtw_scene* s, uint64_t n, const void* rays, const void* hits) {
+  if (!s || (n && (!rays || !hits))) return fail(RTW_EINVAL, "NULL argument");
+  if (!s->s.flattened) return fail(RTW_ESTATE, "scene not committed");
+  return RTW_OK;
+}
+
+int rtw_hit_rays(rtw_scene* s, int device, uint64_t n, const void* rays, void* hits, rtw_stats* stats) {
+  auto t0 = std::chrono::steady_clock::now();
+  if (int e = hit_rays_check(s, n, rays, hits)) return e;
+  rtw_stats st{};
+  if (n == 0) {
+    if (stats) *stats = st;
+    return RTW_OK;
+  }
+  const rtw_ray* r = static_cast<const rtw_ray*>(rays);
+  const float lo = s->s.flat.time_lo, hi = s->s.flat.time_hi;
+  for (uint64_t k = 0; k < n; ++k)
+    if (!(r[k].time >= lo && r[k].time <= hi))
+      return fail(RTW_EINVAL, "ray %llu: time %g outside the committed motion range [%g, %g]", (unsigned long long)k,
+                  r[k].time, lo, hi);
+  DeviceCopy* c = need_copy(s->s, device, device < 0 ? nullptr : "");
+  if (!c) return RTW_ENODEV;
+  DeviceGuard g;
+  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
+  if (int e = check_guard(*c)) return e;
+  if (int e = copy_events(*c)) return e;
+  constexpr uint64_t CHUNK = 1ull << 20;
+  const uint64_t cap = std::min(n, CHUNK);
+  if (int e = grow(c->qrays, cap * sizeof(rtw_ray))) return e;
+  if (int e = grow(c->qhits, cap * sizeof(rtw_hit))) return e;
+  rtw_hit* out = static_cast<rtw_hit*>(hits);
+  for (uint64_t k = 0; k < n; k += CHUNK) {
+    const uint64_t m = std::min(CHUNK, n - k);
+    HIPCHK(hipMemcpy(c->qrays.p, r + k, m * sizeof(rtw_ray), hipMemcpyHostToDevice), "hipMemcpy(rays)");
+    if (int e = enqueue_hit_rays(s->s, *c, m, c->qrays.p, c->qhits.p, nullptr, c->ev[0], c->ev[1])) return e;
+    HIPCHK(hipMemcpy(out + k, c->qhits.p, m * sizeof(rtw_hit), hipMemcpyDeviceToHost), "hipMemcpy(hits)");
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]), "hipEventElapsedTime");
+    st.kernel_ms += ms;
+    if (int e = check_guard(*c)) return e;
+  }
+  st.rays = n;
+  st.total_ms = ms_since(t0);
+  if (stats) *stats = st;
+  return RTW_OK;
+}
+
+int rtw_hit_rays_device(rtw_scene* s, int device, uint64_t n, const void* d_rays, void* d_hits, void* stream,
+                        rtw_stats* stats) {
+  auto t0 = std::chrono::steady_clock::now();
+  if (int e = hit_rays_check(s, n, d_rays, d_hits)) return e;
+  rtw_stats st{};
+  if (n == 0) {
+    if (stats) *stats = st;
+    return RTW_OK;
+  }
+  if (((uintptr_t)d_rays | (uintptr_t)d_hits) & 15u) return fail(RTW_EINVAL, "d_rays and d_hits must be 16-byte aligned");
+  DeviceCopy* c = need_copy(s->s, device, device < 0 ? nullptr : "");
+  if (!c) return RTW_ENODEV;
+  DeviceGuard g;
+  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
+  if (int e = check_guard(*c)) return e;
+  if (stats)
+    if (int e = copy_events(*c)) return e;
+  const hipEvent_t e0 = stats ? c->ev[0] : nullptr, e1 = stats ? c->ev[1] : nullptr;
+  const hipStream_t st_ = abi_stream(stream);
+  if (int e = enqueue_hit_rays(s->s, *c, n, d_rays, d_hits, st_, e0, e1)) return e;
+  if (stats) {
+    HIPCHK(hipStreamSynchronize(st_), "hit_kernel");
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime");
+    if (int e = check_guard(*c)) return e;
+    st.rays = n;
+    st.kernel_ms = ms;
+    st.total_ms = ms_since(t0);
+    *stats = st;
+  }
+  return RTW_OK;
 }
 
 int rtw_render_status(rtw_scene* s, int device) {

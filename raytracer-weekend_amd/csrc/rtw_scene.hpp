@@ -113,6 +113,9 @@ struct DeviceCopy {
   // device buffers kept across render calls (grown, never shrunk; freed by release()): a
   // 30-camera animation through rtw_render does no hipMalloc after the first frame
   DevBuf image, tiles, packed, gathered, gather_ids;
+  DevBuf qrays, qhits;                     // rtw_hit_rays' staging: one chunk of rays and of records
+  int hit_grid = 0;                        // resident hit_kernel grid of the
+  const void* hit_grid_fn = nullptr;       // variant it was computed for
   hipEvent_t ev[2] = {nullptr, nullptr};   // pair timing rtw_render / multi calls (copy_events)
   hipStream_t stream = nullptr;            // rtw_render_multi's stream on this device
   hipEvent_t gev[2] = {nullptr, nullptr};  // pair around rtw_render_multi's gather (device 0)
@@ -126,6 +129,7 @@ struct Scene {
   std::vector<float> tri_v, tri_n, tri_uv;  // per triangle: 9, 9, 6 floats (raw inputs)
   std::vector<uint8_t> tri_nm, tri_uvm;     // per triangle: normal / uv presence masks
   bool committed = false;
+  bool flattened = false;  // rtw_scene_commit got past the flattener (flat is valid), with or without a device
   Flat flat;
   std::vector<DeviceCopy> dev;
   // the last rtw_render_multi call: per-device render ms (path kernel + in-order reduction) and device 0's
@@ -215,6 +219,10 @@ int64_t selected_kernel_info(const Scene& s, int field);
 // ev0 / ev1 (or NULL) are recorded around it
 int enqueue_render(Scene& s, DeviceCopy& c, const Frame& f, const TileSet& tiles, float* d_out, hipStream_t stream,
                    uint32_t flags, hipEvent_t ev0, hipEvent_t ev1);
+// enqueue one closest-hit query of n rays (rtw_ray[n] -> rtw_hit[n], device arrays) on `stream` of c.device, which
+// must be current; ev0 / ev1 (or NULL) are recorded around the kernel
+int enqueue_hit_rays(Scene& s, DeviceCopy& c, uint64_t n, const void* d_rays, void* d_hits, hipStream_t stream,
+                     hipEvent_t ev0, hipEvent_t ev1);
 int enqueue_unpack(uint32_t w, uint32_t h, const uint32_t* d_tiles, uint32_t n_tiles, const float* d_packed,
                    float* d_image, hipStream_t stream);
 

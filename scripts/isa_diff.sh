@@ -6,7 +6,10 @@
 # resource comments.  Normalised before the comparison, and nothing else: the per-compilation __hip_cuid_<hash> symbol
 # and the per-unit function index in local labels (.LBB<fn>_<n> and the loop comments' BB<fn>_<n>, .Lfunc_end<fn>,
 # .Ltmp<n>), with the padding in front of a comment, which moves with a label's length.
-# Prints "identical N/N" per unit, or the first differing kernel and the head of its diff; exit status 1 if any differs.
+# Compares the kernels both revisions have and lists those only one of them has ("only in REV") separately: a revision
+# that adds or retires kernels is still compared on the rest.
+# Prints "identical N/N" per unit, or the first differing kernel and the head of its diff; exit status 1 if any kernel
+# both revisions have differs.
 set -e
 [ $# -eq 2 ] || { echo "usage: $0 REV_A REV_B" >&2; exit 2; }
 ROOT="$(git -C "$(dirname "$0")" rev-parse --show-toplevel)"
@@ -49,19 +52,18 @@ def kernels(path):
 bad = 0
 for unit in ('main', 'mesh'):
     a, b = kernels(f'{tmp}/a.{unit}.s'), kernels(f'{tmp}/b.{unit}.s')
-    n_kern = sum(1 for v in a.values() if any(l.startswith('\t.amdhsa_kernel ') for l in v))
-    if set(a) != set(b):
-        bad = 1
-        for n in sorted(set(a) ^ set(b)):
-            print(f'{unit} unit: {n} only in {rev_a if n in a else rev_b}')
-        continue
-    diff = next((n for n in a if a[n] != b[n]), None)
+    for n in sorted(set(a) ^ set(b)):
+        print(f'{unit} unit: {n} only in {rev_a if n in a else rev_b}')
+    shared = [n for n in a if n in b]
+    n_kern = sum(1 for n in shared if any(l.startswith('\t.amdhsa_kernel ') for l in a[n]))
+    diff = next((n for n in shared if a[n] != b[n]), None)
     if diff is None:
-        print(f'{unit} unit: identical {len(a)}/{len(a)} ({n_kern} kernels, {sum(map(len, a.values()))} lines)')
+        print(f'{unit} unit: identical {len(shared)}/{len(shared)} ({n_kern} kernels, '
+              f'{sum(len(a[n]) for n in shared)} lines)')
         continue
     bad = 1
-    same = sum(a[n] == b[n] for n in a)
-    print(f'{unit} unit: identical {same}/{len(a)}; first differing kernel: {diff}')
+    same = sum(a[n] == b[n] for n in shared)
+    print(f'{unit} unit: identical {same}/{len(shared)}; first differing kernel: {diff}')
     print('\n'.join(list(difflib.unified_diff(a[diff], b[diff], rev_a, rev_b, lineterm='', n=1))[:40]))
 sys.exit(bad)
 PY
