@@ -282,6 +282,57 @@ int rtw_hit_rays(rtw_scene* s, int device, uint64_t n, const void* rays, void* h
 int rtw_hit_rays_device(rtw_scene* s, int device, uint64_t n, const void* d_rays, void* d_hits, void* stream,
                         rtw_stats* stats);
 
+/* ---- scatter and camera-ray queries: the other half of a caller's own integrator.  Camera::get_ray (camera.rs:66-74)
+ *      and Material::scatter + Material::emitted (material.rs:23-26, light_source.rs:17-24) as batch queries over the
+ *      committed scene's own material and texture tables, with the render's f32 operations and draw order:
+ *      rtw_camera_rays -> (rtw_hit_rays -> rtw_scatter_rays)* reproduces rtw_render's samples bit for bit, with the
+ *      same number of rays.  These kernels read only immutable scene tables -- no traversal-stack spill area, path
+ *      queue or sample buffer -- so, unlike renders and rtw_hit_rays*, they need not be serialised with the scene's other
+ *      work on the device. */
+/* material.rs:18-21 Scatter{attenuation, scattered} + Material::emitted: one step of sample_ray after world.hit
+ * (lib.rs:102-116) */
+typedef struct {
+  float attenuation[3]; /* Scatter::attenuation; (1,1,1) for a Dielectric; 0 when not scattered */
+  float emitted[3];     /* Material::emitted (DiffuseLight: its texture's value; else 0); a miss: the background */
+  uint32_t flags, reserved;
+} rtw_scatter;
+enum {
+  RTW_SCATTER_SCATTERED = 1, /* scatter() returned Some: the out ray is valid, continue with T *= attenuation */
+  RTW_SCATTER_MISS = 2,      /* the hit record was a miss: emitted = background (lib.rs:102-105) */
+  RTW_SCATTER_BAD = 4        /* not shaded: material id out of range, an RTW_HIT_BAD_RAY record, or stream word 0 */
+};
+/* The camera rays of paths [first, first + n) of a w x h x spp frame, blocking: `rays` receives rtw_ray[n].  Ray k is
+ * path p = first + k in the reference's emission order, the layout of rtw_render's output: with row = h-1-j,
+ * p = (row*w + i)*spp + sample.  It is the render's ray for (seed, j, i, sample) -- origin, direction and time per
+ * lib.rs:84-86 and camera.rs:66-74 -- and its `stream` is the path's generator state after the time draw, the word the
+ * first segment's rtw_hit_rays keys media with and rtw_scatter_rays draws from.  RTW_EINVAL: a NULL argument; an image
+ * under 2x2 or a side above 65536; first + n > w*h*spp; a camera shutter outside the committed motion range (the
+ * checks of the render calls).  RTW_ESTATE / RTW_ENODEV / n = 0 as rtw_hit_rays.  stats (may be NULL): kernel_ms and
+ * total_ms only. */
+int rtw_camera_rays(rtw_scene* s, int device, const rtw_camera* cam, uint32_t w, uint32_t h, uint32_t spp,
+                    uint64_t seed, uint64_t first, uint64_t n, void* rays, rtw_stats* stats);
+/* The same into a DEVICE array (16-byte aligned) on the caller's `stream`; only enqueues unless stats != NULL. */
+int rtw_camera_rays_device(rtw_scene* s, int device, const rtw_camera* cam, uint32_t w, uint32_t h, uint32_t spp,
+                           uint64_t seed, uint64_t first, uint64_t n, void* d_rays, void* stream, rtw_stats* stats);
+/* One shading step for n (ray, hit record) pairs from host memory, blocking: `rays` is rtw_ray[n] and `hits` rtw_hit[n]
+ * as rtw_hit_rays consumed and produced them (read: the ray's direction, time and stream; the record's p, normal, u, v,
+ * material and flags); `out_rays` receives rtw_ray[n], `out_scatter` rtw_scatter[n].  A scattered ray has origin = p,
+ * the material's direction (not normalised), the time kept and `stream` = the generator state after this material's
+ * draws: it can be fed straight to the next rtw_hit_rays.  Per record: a miss -> RTW_SCATTER_MISS, emitted =
+ * background, the ray copied through; a DiffuseLight -> emitted = its texture at (u, v, p), no flag, no draws, stream
+ * unchanged; an absorbed Metal ray -> no flag, emitted 0, stream advanced; a record that cannot be shaded ->
+ * RTW_SCATTER_BAD, every other output 0.  out_rays may be `rays` (in place); out_scatter may alias nothing.
+ * RTW_EINVAL: a NULL argument with n > 0, or a record whose stream word is 0 (xoroshiro64* never leaves that state;
+ * found by a host scan before anything is enqueued).  RTW_ESTATE / RTW_ENODEV / n = 0 / the staging (2^20 records at
+ * a time) as rtw_hit_rays.  stats (may be NULL): kernel_ms and total_ms only. */
+int rtw_scatter_rays(rtw_scene* s, int device, uint64_t n, const void* rays, const void* hits,
+                     const float background[3], void* out_rays, void* out_scatter, rtw_stats* stats);
+/* The same over DEVICE arrays (16-byte aligned) on the caller's `stream`; only enqueues unless stats != NULL.  No host
+ * scan: a record whose stream word is 0 comes back RTW_SCATTER_BAD. */
+int rtw_scatter_rays_device(rtw_scene* s, int device, uint64_t n, const void* d_rays, const void* d_hits,
+                            const float background[3], void* d_out_rays, void* d_out_scatter, void* stream,
+                            rtw_stats* stats);
+
 /* Errors of renders the caller did not wait for.  A path kernel whose BVH walk trips its guard (a
  * corrupt tree: the walk is bounded, and the first trip closes the path queue, so the grid drains after
  * about one trip per wave) sets the device's host-mapped error word.  It is reported, and cleared, as

@@ -87,7 +87,15 @@ class rtw_hit(C.Structure):  # hittable/mod.rs:22-29 HitRecord
                 ("v", C.c_float), ("material", C.c_uint32), ("key", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class rtw_scatter(C.Structure):  # material.rs:18-21 Scatter + Material::emitted (include/rtw.h)
+    _fields_ = [("attenuation", C.c_float * 3), ("emitted", C.c_float * 3), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 HIT_HIT, HIT_FRONT_FACE, HIT_BAD_RAY = 1, 2, 4
+SCATTER_SCATTERED, SCATTER_MISS, SCATTER_BAD = 1, 2, 4
+SCATTER_DTYPE = np.dtype([("attenuation", np.float32, 3), ("emitted", np.float32, 3), ("flags", np.uint32),
+                          ("reserved", np.uint32)])
 RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("direction", np.float32, 3), ("time", np.float32),
                       ("reserved", np.uint32), ("stream", np.uint64)])
 HIT_DTYPE = np.dtype([("p", np.float32, 3), ("normal", np.float32, 3), ("t", np.float32), ("u", np.float32),
@@ -143,6 +151,15 @@ _SIGS = {
                                C.POINTER(rtw_stats)]),
     "rtw_hit_rays_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.POINTER(rtw_stats)]),
+    "rtw_camera_rays": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(rtw_camera), C.c_uint32, C.c_uint32, C.c_uint32,
+                                  C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(rtw_ray), C.POINTER(rtw_stats)]),
+    "rtw_camera_rays_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(rtw_camera), C.c_uint32, C.c_uint32,
+                                         C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
+                                         C.POINTER(rtw_stats)]),
+    "rtw_scatter_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(rtw_ray), C.POINTER(rtw_hit), _F,
+                                   C.POINTER(rtw_ray), C.POINTER(rtw_scatter), C.POINTER(rtw_stats)]),
+    "rtw_scatter_rays_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, _F, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.POINTER(rtw_stats)]),
     "rtw_render_status": (C.c_int, [C.c_void_p, C.c_int]),
     "rtw_diag_corrupt_bvh": (C.c_int, [C.c_void_p, C.c_int]),
     "rtw_diag_alias_devices": (C.c_int, [C.c_void_p, C.c_int]),
@@ -459,6 +476,56 @@ class Scene:
         st = rtw_stats()
         _check(lib().rtw_hit_rays_device(self._p, device, n, C.c_void_p(d_rays_ptr), C.c_void_p(d_hits_ptr),
                                          C.c_void_p(stream_ptr), C.byref(st) if want_stats else None))
+        return st.as_dict() if want_stats else None
+
+    def camera_rays(self, cam: "Camera", w: int, h: int, spp: int, seed: int, first: int = 0, n=None,
+                    device: int = -1, want_stats: bool = False):
+        """Camera::get_ray as the render calls it (lib.rs:84-86, camera.rs:66-74): the rays of paths [first, first + n)
+        of a w x h x spp frame in rtw_render's output order, p = ((h-1-j)*w + i)*spp + sample (n = None: to the
+        frame's end), each with its path's stream word after the camera's draws.  -> RAY_DTYPE records[, stats]."""
+        n = w * h * spp - first if n is None else n
+        rays = np.zeros(max(n, 0), RAY_DTYPE)
+        st = rtw_stats()
+        _check(lib().rtw_camera_rays(self._p, device, C.byref(cam.c), w, h, spp, seed, first, n,
+                                     rays.ctypes.data_as(C.POINTER(rtw_ray)), C.byref(st)))
+        return (rays, st.as_dict()) if want_stats else rays
+
+    def camera_rays_device(self, cam: "Camera", w: int, h: int, spp: int, seed: int, first: int, n: int,
+                           d_rays_ptr: int, device: int = 0, stream_ptr: int = 0, want_stats: bool = False):
+        """Enqueue the same into device memory (rtw_ray[n], 16-byte aligned) on a stream; waits only for stats."""
+        st = rtw_stats()
+        _check(lib().rtw_camera_rays_device(self._p, device, C.byref(cam.c), w, h, spp, seed, first, n,
+                                            C.c_void_p(d_rays_ptr), C.c_void_p(stream_ptr),
+                                            C.byref(st) if want_stats else None))
+        return st.as_dict() if want_stats else None
+
+    def scatter_rays(self, rays, hits, background, device: int = -1, want_stats: bool = False):
+        """Material::scatter + Material::emitted (material.rs:23-26, light_source.rs:17-24; a miss: the background,
+        lib.rs:102-105) for RAY_DTYPE rays and the HIT_DTYPE records hit_rays gave for them.
+        -> (out_rays as RAY_DTYPE, scatter as SCATTER_DTYPE)[, stats]."""
+        rays = np.ascontiguousarray(rays, RAY_DTYPE)
+        hits = np.ascontiguousarray(hits, HIT_DTYPE)
+        if len(rays) != len(hits):
+            raise ValueError("rays and hits differ in length")
+        out = np.zeros(len(rays), RAY_DTYPE)
+        sc = np.zeros(len(rays), SCATTER_DTYPE)
+        st = rtw_stats()
+        _check(lib().rtw_scatter_rays(self._p, device, len(rays), rays.ctypes.data_as(C.POINTER(rtw_ray)),
+                                      hits.ctypes.data_as(C.POINTER(rtw_hit)), _fp(_fa(background)),
+                                      out.ctypes.data_as(C.POINTER(rtw_ray)),
+                                      sc.ctypes.data_as(C.POINTER(rtw_scatter)), C.byref(st)))
+        return (out, sc, st.as_dict()) if want_stats else (out, sc)
+
+    def scatter_rays_device(self, d_rays_ptr: int, d_hits_ptr: int, background, d_out_rays_ptr: int,
+                            d_out_scatter_ptr: int, n: int, device: int = 0, stream_ptr: int = 0,
+                            want_stats: bool = False):
+        """Enqueue the same over device arrays (16-byte aligned; d_out_rays_ptr may be d_rays_ptr) on a stream; waits
+        only for stats."""
+        st = rtw_stats()
+        _check(lib().rtw_scatter_rays_device(self._p, device, n, C.c_void_p(d_rays_ptr), C.c_void_p(d_hits_ptr),
+                                             _fp(_fa(background)), C.c_void_p(d_out_rays_ptr),
+                                             C.c_void_p(d_out_scatter_ptr), C.c_void_p(stream_ptr),
+                                             C.byref(st) if want_stats else None))
         return st.as_dict() if want_stats else None
 
     def render_status(self, device: int = -1) -> None:

@@ -13,6 +13,8 @@
 //   load_wavefront_obj(path, rng)                       world.load_wavefront_obj(path)
 //   Raytracer::new(..).render() -> Pixel stream         Raytracer(..).render() -> std::vector<Pixel>
 //   world.hit(&ray, 0.001, INFINITY) -> Option<HitRecord>  world.hit_rays(rays) -> std::vector<Hit>  hittable/mod.rs:22-69
+//   cam.get_ray(u, v, rng) per path of a frame          world.camera_rays(cam, w, h, spp, seed) -> std::vector<Ray>  camera.rs:66-74
+//   rec.material.scatter(&ray, &rec, rng) / emitted()   world.scatter_rays(rays, hits, background) -> {rays, Scatter}  material.rs:23-26
 // Errors (the reference panics) throw rtw::Error with rtw_last_error()'s message.
 #pragma once
 #include <stdexcept>
@@ -65,6 +67,15 @@ struct Hit {
   bool front_face() const { return flags & RTW_HIT_FRONT_FACE; }
 };
 static_assert(sizeof(Ray) == sizeof(rtw_ray) && sizeof(Hit) == sizeof(rtw_hit), "rtw::Ray / rtw::Hit mirror rtw.h");
+// material.rs:18-21 Scatter + Material::emitted: one step of sample_ray after world.hit, laid out as rtw_scatter
+struct Scatter {
+  Color attenuation, emitted;
+  uint32_t flags, reserved;
+  bool scattered() const { return flags & RTW_SCATTER_SCATTERED; }
+  bool miss() const { return flags & RTW_SCATTER_MISS; }
+  bool bad() const { return flags & RTW_SCATTER_BAD; }
+};
+static_assert(sizeof(Scatter) == sizeof(rtw_scatter), "rtw::Scatter mirrors rtw.h");
 
 struct Camera {
   rtw_camera c{};
@@ -160,6 +171,26 @@ class World {
     std::vector<Hit> hits(rays.size());
     check(rtw_hit_rays(s_, device, rays.size(), rays.data(), hits.data(), st));
     return hits;
+  }
+  // the render's camera rays of paths [first, first + n) of a w x h x spp frame, in rtw_render's output order
+  // (lib.rs:84-86, camera.rs:66-74); n = UINT64_MAX: to the frame's end
+  std::vector<Ray> camera_rays(const Camera& cam, uint32_t w, uint32_t h, uint32_t spp, uint64_t seed,
+                               uint64_t first = 0, uint64_t n = UINT64_MAX, int device = -1,
+                               rtw_stats* st = nullptr) const {
+    const uint64_t paths = (uint64_t)w * h * spp;
+    if (n == UINT64_MAX) n = first <= paths ? paths - first : 0;
+    std::vector<Ray> rays(n);
+    check(rtw_camera_rays(s_, device, &cam.c, w, h, spp, seed, first, n, rays.data(), st));
+    return rays;
+  }
+  // Material::scatter + emitted for every (ray, hit record) pair (lib.rs:102-116): the scattered rays replace `rays`
+  std::vector<Scatter> scatter_rays(std::vector<Ray>& rays, const std::vector<Hit>& hits, Color background,
+                                    int device = -1, rtw_stats* st = nullptr) const {
+    if (rays.size() != hits.size()) throw Error(RTW_EINVAL, "rays and hits differ in length");
+    std::vector<Scatter> sc(rays.size());
+    const float bg[3] = {background.x, background.y, background.z};
+    check(rtw_scatter_rays(s_, device, rays.size(), rays.data(), hits.data(), bg, rays.data(), sc.data(), st));
+    return sc;
   }
 
  private:

@@ -652,6 +652,49 @@ bool texture_reads_uv(const Scene& s, uint32_t t, int guard = 0) {
   return false;
 }
 
+// A material's shading record (DevShade, rtw_device.hpp): a function of the material and its texture alone, read per
+// primitive by the path kernel (Flat::shade) and per material by rtw_scatter_rays (Flat::mshade).
+DevShade shade_record(const Flat& f, const DevMat& m) {
+  DevShade d;
+  memset(&d, 0, sizeof d);
+  uint32_t mode = SM_GENERIC;
+  if (m.type == MT_METAL) {
+    mode = SM_SOLID;
+    memcpy(d.a, m.albedo, sizeof d.a);
+    d.param = m.param;
+  } else if (m.type == MT_DIELECTRIC) {
+    mode = SM_SOLID;  // attenuation (1, 1, 1), no texture
+    d.param = m.param;
+    // material.rs:120 (1.0 / ir) and :108-112 (Schlick r0) for both refraction ratios: the kernel's
+    // f32 operations, evaluated once here (IEEE f32 on the host as on the device)
+    const volatile float one = 1.0f;
+    auto r0 = [&](float ri) {
+      const float x = (one - ri) / (one + ri);
+      return x * x;
+    };
+    d.a[0] = one / m.param;
+    d.a[1] = r0(d.a[0]);
+    d.a[2] = r0(m.param);
+  } else {  // Lambertian, DiffuseLight, Isotropic: a texture
+    const DevTex& t = f.texs[m.tex];
+    if (t.type == TT_SOLID) {
+      mode = SM_SOLID;
+      memcpy(d.a, t.c, sizeof d.a);
+    } else if (t.type == TT_CHECKER && f.texs[t.odd].type == TT_SOLID && f.texs[t.even].type == TT_SOLID) {
+      mode = SM_CHECKER;
+      memcpy(d.a, f.texs[t.odd].c, sizeof d.a);
+      memcpy(d.b, f.texs[t.even].c, sizeof d.b);
+      d.param = t.freq;
+    } else if (t.type == TT_IMAGE) {  // the texel lookup needs no material / texture record loads
+      mode = SM_IMAGE;
+      const uint32_t img[3] = {t.off, t.w, t.h};
+      memcpy(d.a, img, sizeof d.a);
+    }
+  }
+  d.kind = m.type | (mode << 8) | (m.needs_uv ? 1u << 12 : 0u);
+  return d;
+}
+
 }  // namespace
 
 int flatten(Scene& s) {
@@ -848,48 +891,14 @@ int flatten(Scene& s) {
     const uint32_t t = p.type_inst & 0xffu;
     if (t == PT_SPHERE || t == PT_MSPHERE) memcpy(&p.q1[3], &p.key, sizeof p.key);
   }
-  // shading records (one per prim, same order)
+  // shading records: one per material (rtw_scatter_rays reads them by the hit record's material id), and the
+  // per-primitive table the path kernel reads, which is the material's record at every prim (same order as prims)
+  f.mshade.clear();
+  for (const DevMat& m : f.mats) f.mshade.push_back(shade_record(f, m));
   for (const DevPrim& p : f.prims) {
-    const DevMat& m = f.mats[p.mat];
-    DevShade d;
-    memset(&d, 0, sizeof d);
-    uint32_t mode = SM_GENERIC;
-    if (m.type == MT_METAL) {
-      mode = SM_SOLID;
-      memcpy(d.a, m.albedo, sizeof d.a);
-      d.param = m.param;
-    } else if (m.type == MT_DIELECTRIC) {
-      mode = SM_SOLID;  // attenuation (1, 1, 1), no texture
-      d.param = m.param;
-      // material.rs:120 (1.0 / ir) and :108-112 (Schlick r0) for both refraction ratios: the kernel's
-      // f32 operations, evaluated once here (IEEE f32 on the host as on the device)
-      const volatile float one = 1.0f;
-      auto r0 = [&](float ri) {
-        const float x = (one - ri) / (one + ri);
-        return x * x;
-      };
-      d.a[0] = one / m.param;
-      d.a[1] = r0(d.a[0]);
-      d.a[2] = r0(m.param);
-    } else {  // Lambertian, DiffuseLight, Isotropic: a texture
-      const DevTex& t = f.texs[m.tex];
-      if (t.type == TT_SOLID) {
-        mode = SM_SOLID;
-        memcpy(d.a, t.c, sizeof d.a);
-      } else if (t.type == TT_CHECKER && f.texs[t.odd].type == TT_SOLID && f.texs[t.even].type == TT_SOLID) {
-        mode = SM_CHECKER;
-        memcpy(d.a, f.texs[t.odd].c, sizeof d.a);
-        memcpy(d.b, f.texs[t.even].c, sizeof d.b);
-        d.param = t.freq;
-      } else if (t.type == TT_IMAGE) {  // the texel lookup needs no material / texture record loads
-        mode = SM_IMAGE;
-        const uint32_t img[3] = {t.off, t.w, t.h};
-        memcpy(d.a, img, sizeof d.a);
-      }
-    }
-    d.kind = m.type | (mode << 8) | (m.needs_uv ? 1u << 12 : 0u);
+    const DevShade& d = f.mshade[p.mat];
     f.shade.push_back(d);
-    if (mode == SM_GENERIC) f.features |= F_TEXGEN;
+    if (((d.kind >> 8) & 0xfu) == SM_GENERIC) f.features |= F_TEXGEN;
   }
   // 4-wide tree for the kernel
   if (!f.nodes.empty()) {

@@ -1,7 +1,7 @@
 // rtw_kernel.hip — what of the gfx950 path-tracing megakernel's host side needs the device compiler: the kernels
 // that are no templates (reduce_kernel, unpack_tiles_kernel, the libm and reciprocal diagnostics, with the two calls
 // that launch the latter), the tuning knobs, pick_kernel (which path-kernel variant a scene runs) and the launches
-// (enqueue_render, enqueue_hit_rays, enqueue_unpack).  The scene's device copies, statistics and the render and
+// (enqueue_render, enqueue_hit_rays, enqueue_scatter_rays, enqueue_camera_rays, enqueue_unpack).  The scene's device copies, statistics and the render and
 // ray-query entry points are plain HIP runtime code in rtw_render.cpp.  The device code is in headers that this unit
 // and rtw_kernel_mesh.hip (the F_MESHES variants, under their own compiler flags) both include.
 //
@@ -34,6 +34,8 @@
 // its radiance to an ordered sample buffer that reduce_kernel sums per pixel in sample order.
 // Ray queries (rtw_hit_rays*): hit_kernel<K> (rtw_query_kernel.hpp) runs caller rays through the same trace_begin /
 // trace_run / hit_record under the scene's own K, one ray per lane, grid-stride; instantiated beside path_kernel<.., K>.
+// Scatter and camera-ray queries (rtw_scatter_rays*, rtw_camera_rays*): scatter_kernel and camera_rays_kernel
+// (rtw_shade_kernel.hpp) restate the materials and start_path over record arrays; one instantiation each, this unit only.
 // Variants: path_kernel<COUNT, KernelCfg K> -- one plain aggregate (stack rows, spill, waves / SIMD, feature set,
 // workgroup size, LDS node table, half nodes, 16-bit stack) is the template argument, defines every property derived
 // from it, and travels with the kernel to the host (Variant, rtw_variants.hpp), which sizes the launch from it.
@@ -53,6 +55,7 @@
 #include "../../include/rtw.h"
 #include "rtw_scene.hpp"
 #include "rtw_variants.hpp"
+#include "rtw_shade_kernel.hpp"
 
 namespace rtw {
 namespace dev {
@@ -486,6 +489,74 @@ int enqueue_hit_rays(Scene& sc, DeviceCopy& c, uint64_t n, const void* d_rays, v
   if (grid > 0) {
     hipLaunchKernelGGL(var.hit, dim3(grid), dim3(k.blk), 0, stream, a);
     HIPCHK(hipGetLastError(), "hit_kernel launch");
+  }
+  if (ev1) HIPCHK(hipEventRecord(ev1, stream), "hipEventRecord");
+  return RTW_OK;
+}
+
+// The record-streaming kernels' grid: 256-lane blocks, at most the kernel's resident capacity (grid-stride beyond it)
+static int shade_grid(DeviceCopy& c, int which, const void* fn, uint64_t n, bool verbose) {
+  int& g = c.shade_grid[which];
+  if (g <= 0) {
+    int per_cu = 0, cus = 0;
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, dev::SHADE_BLOCK, 0);
+    if (e != hipSuccess || per_cu < 1) per_cu = 1;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.phys) != hipSuccess || cus < 1) cus = 256;
+    g = per_cu * cus;
+    if (verbose)
+      fprintf(stderr, "rtw: %s: block %d, %d resident blocks per CU x %d CUs\n",
+              which ? "camera_rays_kernel" : "scatter_kernel", dev::SHADE_BLOCK, per_cu, cus);
+  }
+  const uint64_t blocks = (n + (uint32_t)dev::SHADE_BLOCK - 1u) / (uint32_t)dev::SHADE_BLOCK;
+  return (int)std::min<uint64_t>((uint64_t)g, blocks);
+}
+
+// Scatter queries (rtw_scatter_rays*): the scene's tables, the per-material shading records and the record arrays.
+int enqueue_scatter_rays(Scene& sc, DeviceCopy& c, uint64_t n, const void* d_rays, const void* d_hits, const float* bg,
+                         void* d_out_rays, void* d_out_scatter, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+  const Knobs kn = read_knobs();
+  ScatterArgs a;
+  memset(&a, 0, sizeof a);
+  a.scene = c.scene;
+  a.mshade = static_cast<const DevShade*>(c.mshade.p);
+  a.n_mats = (uint32_t)sc.flat.mshade.size();
+  memcpy(a.bg, bg, sizeof a.bg);
+  a.rays = d_rays;
+  a.hits = d_hits;
+  a.out_rays = d_out_rays;
+  a.out_scatter = d_out_scatter;
+  a.n = n;
+  const int grid = shade_grid(c, 0, (const void*)dev::scatter_kernel, n, kn.verbose);
+  if (ev0) HIPCHK(hipEventRecord(ev0, stream), "hipEventRecord");
+  if (grid > 0) {
+    hipLaunchKernelGGL(dev::scatter_kernel, dim3(grid), dim3(dev::SHADE_BLOCK), 0, stream, a);
+    HIPCHK(hipGetLastError(), "scatter_kernel launch");
+  }
+  if (ev1) HIPCHK(hipEventRecord(ev1, stream), "hipEventRecord");
+  return RTW_OK;
+}
+
+// Camera-ray queries (rtw_camera_rays*): start_path's operands as frame_args computes them for a render of the frame.
+int enqueue_camera_rays(DeviceCopy& c, const Frame& f, uint64_t first, uint64_t n, void* d_rays, hipStream_t stream,
+                        hipEvent_t ev0, hipEvent_t ev1) {
+  const Knobs kn = read_knobs();
+  const RenderArgs r = frame_args(c, f, TileSet{}, nullptr);
+  CameraRaysArgs a;
+  memset(&a, 0, sizeof a);
+  a.cam = r.cam;
+  a.fw1 = r.fw1; a.fh1 = r.fh1; a.rw1 = r.rw1; a.rh1 = r.rh1; a.time_span = r.time_span;
+  a.w = f.w; a.spp = f.spp;
+  a.row_paths = (uint64_t)f.w * f.spp;
+  a.h1 = f.h - 1u;
+  a.seed_hash = r.seed_hash;
+  a.first = first;
+  a.n = n;
+  a.rays = d_rays;
+  const int grid = shade_grid(c, 1, (const void*)dev::camera_rays_kernel, n, kn.verbose);
+  if (ev0) HIPCHK(hipEventRecord(ev0, stream), "hipEventRecord");
+  if (grid > 0) {
+    hipLaunchKernelGGL(dev::camera_rays_kernel, dim3(grid), dim3(dev::SHADE_BLOCK), 0, stream, a);
+    HIPCHK(hipGetLastError(), "camera_rays_kernel launch");
   }
   if (ev1) HIPCHK(hipEventRecord(ev1, stream), "hipEventRecord");
   return RTW_OK;

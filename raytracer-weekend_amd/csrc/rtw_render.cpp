@@ -2,7 +2,7 @@
 // the grow-only buffers), the render calls' shared opening (check_frame, need_copy), statistics, the traversal guard's
 // error word, and the render / ray-query / status entry points of one device.  Plain HIP runtime API: the kernels, which
 // variant a scene runs and how a render or a query is enqueued are rtw_kernel.hip's (enqueue_render, enqueue_hit_rays,
-// enqueue_unpack); the render over several devices is rtw_multi.cpp's.
+// enqueue_scatter_rays, enqueue_camera_rays, enqueue_unpack); the render over several devices is rtw_multi.cpp's.
 #include <math.h>
 #include <string.h>
 
@@ -55,6 +55,12 @@ int upload(Scene& s, int device) {
     // mapped): the host reads it without a device round trip, also for renders it did not wait for
     HIPCHK(hipHostMalloc((void**)&c.err_host, 64, hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc(error word)");
     *(volatile uint32_t*)c.err_host = 0u;
+    // the per-material shading records (rtw_scatter_rays): a buffer of their own, so the scene block's layout stays
+    if (!f.mshade.empty()) {
+      if (int e = grow(c.mshade, f.mshade.size() * sizeof(DevShade))) return e;
+      HIPCHK(hipMemcpy(c.mshade.p, f.mshade.data(), f.mshade.size() * sizeof(DevShade), hipMemcpyHostToDevice),
+             "hipMemcpy(material shading records)");
+    }
     uint8_t* base = (uint8_t*)c.block;
     c.scene.nodes = (const DevNode4*)(base + o_nodes);
     c.scene.hnodes = f.nodes4h.empty() ? nullptr : (const DevNode4h*)(base + o_hnodes);
@@ -104,7 +110,8 @@ void release(Scene& s) {
     if (c.block) hipFree(c.block);
     if (c.counters) hipFree(c.counters);
     if (c.err_host) hipHostFree(c.err_host);
-    for (DevBuf* b : {&c.sbuf, &c.spill, &c.image, &c.tiles, &c.packed, &c.gathered, &c.gather_ids, &c.qrays, &c.qhits})
+    for (DevBuf* b : {&c.sbuf, &c.spill, &c.image, &c.tiles, &c.packed, &c.gathered, &c.gather_ids, &c.qrays, &c.qhits,
+                       &c.mshade, &c.qscatter})
       free_buf(*b);
     for (hipEvent_t e : {c.ev[0], c.ev[1], c.gev[0], c.gev[1]})
       if (e) hipEventDestroy(e);
@@ -346,6 +353,177 @@ int rtw_hit_rays_device(rtw_scene* s, int device, uint64_t n, const void* d_rays
     HIPCHK(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime");
     if (int e = check_guard(*c)) return e;
     st.rays = n;
+    st.kernel_ms = ms;
+    st.total_ms = ms_since(t0);
+    *stats = st;
+  }
+  return RTW_OK;
+}
+
+// rtw_camera_rays and rtw_camera_rays_device: hit_rays_check (the camera as its first array), then the frame and the
+// shutter as the render calls check them (check_frame, enqueue_render) and the path range.  Host only.
+static int camera_rays_check(const rtw_scene* s, const rtw_camera* cam, uint32_t w, uint32_t h, uint32_t spp,
+                             uint64_t first, uint64_t n, const void* rays) {
+  if (!s || !cam || (n && !rays)) return fail(RTW_EINVAL, "NULL argument");
+  if (int e = hit_rays_check(s, n, cam, rays)) return e;
+  if (w < 2 || h < 2) return fail(RTW_EINVAL, "image must be at least 2x2 (lib.rs:84-85 divides by w-1, h-1)");
+  if (w > 65536u || h > 65536u)
+    return fail(RTW_EINVAL, "image %ux%u: at most 65536 x 65536 (16-bit pixel coordinates in the path key)", w, h);
+  const uint64_t paths = (uint64_t)w * h * spp;  // < 2^64: w * h <= 2^32
+  if (first > paths || n > paths - first)
+    return fail(RTW_EINVAL, "paths [%llu, %llu + %llu) leave the frame's %llu", (unsigned long long)first,
+                (unsigned long long)first, (unsigned long long)n, (unsigned long long)paths);
+  if (cam->time0 < s->s.flat.time_lo || cam->time1 > s->s.flat.time_hi)
+    return fail(RTW_EINVAL, "camera shutter [%g, %g) outside the committed motion range [%g, %g]", cam->time0,
+                cam->time1, s->s.flat.time_lo, s->s.flat.time_hi);
+  // (a camera filled in by hand: the time draw's retry loop ends only for a non-empty range; camera.rs:72 panics)
+  if (!(cam->time0 < cam->time1)) return fail(RTW_EINVAL, "camera shutter [%g, %g) is empty", cam->time0, cam->time1);
+  return RTW_OK;
+}
+
+int rtw_camera_rays(rtw_scene* s, int device, const rtw_camera* cam, uint32_t w, uint32_t h, uint32_t spp,
+                    uint64_t seed, uint64_t first, uint64_t n, void* rays, rtw_stats* stats) {
+  auto t0 = std::chrono::steady_clock::now();
+  if (int e = camera_rays_check(s, cam, w, h, spp, first, n, rays)) return e;
+  rtw_stats st{};
+  if (n == 0) {
+    if (stats) *stats = st;
+    return RTW_OK;
+  }
+  DeviceCopy* c = need_copy(s->s, device, device < 0 ? nullptr : "");
+  if (!c) return RTW_ENODEV;
+  DeviceGuard g;
+  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
+  if (int e = copy_events(*c)) return e;
+  constexpr uint64_t CHUNK = 1ull << 20;
+  if (int e = grow(c->qrays, std::min(n, CHUNK) * sizeof(rtw_ray))) return e;
+  const float no_bg[3] = {0.f, 0.f, 0.f};
+  const Frame f{cam, no_bg, w, h, spp, 0, seed};
+  rtw_ray* out = static_cast<rtw_ray*>(rays);
+  for (uint64_t k = 0; k < n; k += CHUNK) {
+    const uint64_t m = std::min(CHUNK, n - k);
+    if (int e = enqueue_camera_rays(*c, f, first + k, m, c->qrays.p, nullptr, c->ev[0], c->ev[1])) return e;
+    HIPCHK(hipMemcpy(out + k, c->qrays.p, m * sizeof(rtw_ray), hipMemcpyDeviceToHost), "hipMemcpy(rays)");
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]), "hipEventElapsedTime");
+    st.kernel_ms += ms;
+  }
+  st.total_ms = ms_since(t0);
+  if (stats) *stats = st;
+  return RTW_OK;
+}
+
+int rtw_camera_rays_device(rtw_scene* s, int device, const rtw_camera* cam, uint32_t w, uint32_t h, uint32_t spp,
+                           uint64_t seed, uint64_t first, uint64_t n, void* d_rays, void* stream, rtw_stats* stats) {
+  auto t0 = std::chrono::steady_clock::now();
+  if (int e = camera_rays_check(s, cam, w, h, spp, first, n, d_rays)) return e;
+  rtw_stats st{};
+  if (n == 0) {
+    if (stats) *stats = st;
+    return RTW_OK;
+  }
+  if ((uintptr_t)d_rays & 15u) return fail(RTW_EINVAL, "d_rays must be 16-byte aligned");
+  DeviceCopy* c = need_copy(s->s, device, device < 0 ? nullptr : "");
+  if (!c) return RTW_ENODEV;
+  DeviceGuard g;
+  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
+  if (stats)
+    if (int e = copy_events(*c)) return e;
+  const hipEvent_t e0 = stats ? c->ev[0] : nullptr, e1 = stats ? c->ev[1] : nullptr;
+  const hipStream_t st_ = abi_stream(stream);
+  const float no_bg[3] = {0.f, 0.f, 0.f};
+  const Frame f{cam, no_bg, w, h, spp, 0, seed};
+  if (int e = enqueue_camera_rays(*c, f, first, n, d_rays, st_, e0, e1)) return e;
+  if (stats) {
+    HIPCHK(hipStreamSynchronize(st_), "camera_rays_kernel");
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime");
+    st.kernel_ms = ms;
+    st.total_ms = ms_since(t0);
+    *stats = st;
+  }
+  return RTW_OK;
+}
+
+// rtw_scatter_rays and rtw_scatter_rays_device: hit_rays_check over all five arrays
+static int scatter_rays_check(const rtw_scene* s, uint64_t n, const void* rays, const void* hits, const float* bg,
+                              const void* out_rays, const void* out_scatter) {
+  if (!s || !bg || (n && (!rays || !hits || !out_rays || !out_scatter))) return fail(RTW_EINVAL, "NULL argument");
+  return hit_rays_check(s, n, rays, hits);
+}
+
+int rtw_scatter_rays(rtw_scene* s, int device, uint64_t n, const void* rays, const void* hits,
+                     const float background[3], void* out_rays, void* out_scatter, rtw_stats* stats) {
+  auto t0 = std::chrono::steady_clock::now();
+  if (int e = scatter_rays_check(s, n, rays, hits, background, out_rays, out_scatter)) return e;
+  rtw_stats st{};
+  if (n == 0) {
+    if (stats) *stats = st;
+    return RTW_OK;
+  }
+  const rtw_ray* r = static_cast<const rtw_ray*>(rays);
+  for (uint64_t k = 0; k < n; ++k)
+    if (r[k].stream == 0)
+      return fail(RTW_EINVAL, "record %llu: stream word 0 (the generator never leaves that state)",
+                  (unsigned long long)k);
+  DeviceCopy* c = need_copy(s->s, device, device < 0 ? nullptr : "");
+  if (!c) return RTW_ENODEV;
+  DeviceGuard g;
+  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
+  if (int e = copy_events(*c)) return e;
+  constexpr uint64_t CHUNK = 1ull << 20;
+  const uint64_t cap = std::min(n, CHUNK);
+  if (int e = grow(c->qrays, cap * sizeof(rtw_ray))) return e;
+  if (int e = grow(c->qhits, cap * sizeof(rtw_hit))) return e;
+  if (int e = grow(c->qscatter, cap * sizeof(rtw_scatter))) return e;
+  const rtw_hit* hr = static_cast<const rtw_hit*>(hits);
+  rtw_ray* out_r = static_cast<rtw_ray*>(out_rays);
+  rtw_scatter* out_s = static_cast<rtw_scatter*>(out_scatter);
+  for (uint64_t k = 0; k < n; k += CHUNK) {
+    const uint64_t m = std::min(CHUNK, n - k);
+    HIPCHK(hipMemcpy(c->qrays.p, r + k, m * sizeof(rtw_ray), hipMemcpyHostToDevice), "hipMemcpy(rays)");
+    HIPCHK(hipMemcpy(c->qhits.p, hr + k, m * sizeof(rtw_hit), hipMemcpyHostToDevice), "hipMemcpy(hits)");
+    // in place on the device: the staged rays become the scattered rays
+    if (int e = enqueue_scatter_rays(s->s, *c, m, c->qrays.p, c->qhits.p, background, c->qrays.p, c->qscatter.p, nullptr,
+                                     c->ev[0], c->ev[1]))
+      return e;
+    HIPCHK(hipMemcpy(out_r + k, c->qrays.p, m * sizeof(rtw_ray), hipMemcpyDeviceToHost), "hipMemcpy(out rays)");
+    HIPCHK(hipMemcpy(out_s + k, c->qscatter.p, m * sizeof(rtw_scatter), hipMemcpyDeviceToHost), "hipMemcpy(scatter)");
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]), "hipEventElapsedTime");
+    st.kernel_ms += ms;
+  }
+  st.total_ms = ms_since(t0);
+  if (stats) *stats = st;
+  return RTW_OK;
+}
+
+int rtw_scatter_rays_device(rtw_scene* s, int device, uint64_t n, const void* d_rays, const void* d_hits,
+                            const float background[3], void* d_out_rays, void* d_out_scatter, void* stream,
+                            rtw_stats* stats) {
+  auto t0 = std::chrono::steady_clock::now();
+  if (int e = scatter_rays_check(s, n, d_rays, d_hits, background, d_out_rays, d_out_scatter)) return e;
+  rtw_stats st{};
+  if (n == 0) {
+    if (stats) *stats = st;
+    return RTW_OK;
+  }
+  if (((uintptr_t)d_rays | (uintptr_t)d_hits | (uintptr_t)d_out_rays | (uintptr_t)d_out_scatter) & 15u)
+    return fail(RTW_EINVAL, "d_rays, d_hits, d_out_rays and d_out_scatter must be 16-byte aligned");
+  DeviceCopy* c = need_copy(s->s, device, device < 0 ? nullptr : "");
+  if (!c) return RTW_ENODEV;
+  DeviceGuard g;
+  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
+  if (stats)
+    if (int e = copy_events(*c)) return e;
+  const hipEvent_t e0 = stats ? c->ev[0] : nullptr, e1 = stats ? c->ev[1] : nullptr;
+  const hipStream_t st_ = abi_stream(stream);
+  if (int e = enqueue_scatter_rays(s->s, *c, n, d_rays, d_hits, background, d_out_rays, d_out_scatter, st_, e0, e1))
+    return e;
+  if (stats) {
+    HIPCHK(hipStreamSynchronize(st_), "scatter_kernel");
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime");
     st.kernel_ms = ms;
     st.total_ms = ms_since(t0);
     *stats = st;

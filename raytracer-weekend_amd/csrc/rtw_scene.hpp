@@ -66,6 +66,7 @@ struct Flat {
   std::vector<DevNode4h> nodes4h;  // nodes4 in half precision (when codes16; rtw_device.hpp)
   std::vector<DevPrim> prims;
   std::vector<DevShade> shade;  // per prim: material + common texture values (rtw_device.hpp)
+  std::vector<DevShade> mshade;  // the same record per material: shade[k] = mshade[prims[k].mat] (rtw_scatter_rays)
   std::vector<uint32_t> always;
   std::vector<DevTriShade> tshade;
   std::vector<DevInst> insts;
@@ -116,6 +117,9 @@ struct DeviceCopy {
   DevBuf qrays, qhits;                     // rtw_hit_rays' staging: one chunk of rays and of records
   int hit_grid = 0;                        // resident hit_kernel grid of the
   const void* hit_grid_fn = nullptr;       // variant it was computed for
+  DevBuf mshade;                           // Flat::mshade (uploaded with the scene; scatter_kernel's material table)
+  DevBuf qscatter;                         // rtw_scatter_rays' staging: one chunk of rtw_scatter records
+  int shade_grid[2] = {0, 0};              // resident grids of scatter_kernel and camera_rays_kernel
   hipEvent_t ev[2] = {nullptr, nullptr};   // pair timing rtw_render / multi calls (copy_events)
   hipStream_t stream = nullptr;            // rtw_render_multi's stream on this device
   hipEvent_t gev[2] = {nullptr, nullptr};  // pair around rtw_render_multi's gather (device 0)
@@ -223,6 +227,14 @@ int enqueue_render(Scene& s, DeviceCopy& c, const Frame& f, const TileSet& tiles
 // must be current; ev0 / ev1 (or NULL) are recorded around the kernel
 int enqueue_hit_rays(Scene& s, DeviceCopy& c, uint64_t n, const void* d_rays, void* d_hits, hipStream_t stream,
                      hipEvent_t ev0, hipEvent_t ev1);
+// enqueue Material::scatter + emitted for n (ray, hit record) pairs (device arrays; d_out_rays may be d_rays) on `stream`
+// of c.device, which must be current; ev0 / ev1 (or NULL) are recorded around the kernel
+int enqueue_scatter_rays(Scene& s, DeviceCopy& c, uint64_t n, const void* d_rays, const void* d_hits, const float* bg,
+                         void* d_out_rays, void* d_out_scatter, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1);
+// enqueue the camera rays of paths [first, first + n) of frame f (its max_depth and bg unused) into d_rays, likewise;
+// the caller has checked the frame and the shutter (rtw_render.cpp camera_rays_check)
+int enqueue_camera_rays(DeviceCopy& c, const Frame& f, uint64_t first, uint64_t n, void* d_rays, hipStream_t stream,
+                        hipEvent_t ev0, hipEvent_t ev1);
 int enqueue_unpack(uint32_t w, uint32_t h, const uint32_t* d_tiles, uint32_t n_tiles, const float* d_packed,
                    float* d_image, hipStream_t stream);
 
