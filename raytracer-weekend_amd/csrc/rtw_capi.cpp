@@ -1,6 +1,7 @@
 // rtw_capi.cpp — builder half of the C-ABI (include/rtw.h): textures, materials,
 // hierarchy, primitives, camera, tonemap and the scene-text dump used by the tests.
-// Render / device entry points live in rtw_render.cpp and rtw_multi.cpp, the kernels and their launches in rtw_kernel.hip.
+// Render / device entry points live in rtw_render.cpp and rtw_multi.cpp, the ray-query ones in rtw_query.cpp, the
+// kernels and their launches in rtw_kernel.hip.
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>

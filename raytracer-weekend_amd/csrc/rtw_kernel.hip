@@ -1,9 +1,11 @@
 // rtw_kernel.hip — what of the gfx950 path-tracing megakernel's host side needs the device compiler: the kernels
 // that are no templates (reduce_kernel, unpack_tiles_kernel, the libm and reciprocal diagnostics, with the two calls
 // that launch the latter), the tuning knobs, pick_kernel (which path-kernel variant a scene runs) and the launches
-// (enqueue_render, enqueue_hit_rays, enqueue_scatter_rays, enqueue_camera_rays, enqueue_unpack).  The scene's device copies, statistics and the render and
-// ray-query entry points are plain HIP runtime code in rtw_render.cpp.  The device code is in headers that this unit
-// and rtw_kernel_mesh.hip (the F_MESHES variants, under their own compiler flags) both include.
+// (enqueue_render, enqueue_hit_rays, enqueue_scatter_rays, enqueue_camera_rays, enqueue_unpack), which share one cache
+// of resident grids (resident_blocks), the walk's tuning (tune_walk) and the queries' launch (launch_query).  The
+// scene's device copies, statistics and the render entry points are plain HIP runtime code in rtw_render.cpp, the
+// ray-query entry points in rtw_query.cpp.  The device code is in headers that this unit and rtw_kernel_mesh.hip (the
+// F_MESHES variants, under their own compiler flags) both include.
 //
 // Hot path restated (reference raytracer_weekend_lib/src/):
 //   Raytracer::render / sample_pixel (lib.rs:57-95)   -> one work unit per path (pixel, sample); the samples
@@ -269,21 +271,35 @@ int64_t selected_kernel_info(const Scene& s, int field) {
   return field >= 0 && field < 8 ? v[field] : -1;
 }
 
-static int resident_grid(DeviceCopy& c, const Variant& var, bool count, bool verbose) {
-  const path_fn fn = var.fn[count];
-  const int block = var.cfg.blk;
-  int& g = c.grid[count ? 1 : 0];
-  const void*& gf = c.grid_fn[count ? 1 : 0];
-  if (g > 0 && gf == (const void*)fn) return g;
-  gf = (const void*)fn;
+// The resident capacity of kernel fn in blocks of `block` lanes on c's device (blocks per CU x CUs): the persistent
+// path kernel's grid and the largest grid of a query kernel.  Computed at first use and when a knob switched the
+// slot's kernel.
+static int resident_blocks(DeviceCopy& c, GridSlot slot, const void* fn, int block, const char* what, bool verbose) {
+  ResidentGrid& g = c.grids[slot];
+  if (g.blocks > 0 && g.fn == fn) return g.blocks;
   int per_cu = 0, cus = 0;
   hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, block, 0);
   if (e != hipSuccess || per_cu < 1) per_cu = 1;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.phys) != hipSuccess || cus < 1) cus = 256;
-  g = per_cu * cus;
+  g = ResidentGrid{fn, per_cu * cus};
   if (verbose)
-    fprintf(stderr, "rtw: path kernel %p: block %d, %d resident blocks per CU x %d CUs\n", (void*)fn, block, per_cu, cus);
-  return g;
+    fprintf(stderr, "rtw: %s %p: block %d, %d resident blocks per CU x %d CUs\n", what, fn, block, per_cu, cus);
+  return g.blocks;
+}
+
+// A query kernel over n records, one per lane, between ev0 and ev1 (or NULL): at most `resident` blocks (the kernels
+// stride by the grid beyond them), none for n = 0
+template <class Kernel, class Args>
+static int launch_query(Kernel kernel, const char* what, int resident, int block, uint64_t n, const Args& a,
+                        hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+  const int grid = (int)std::min<uint64_t>((uint64_t)resident, (n + (uint32_t)block - 1u) / (uint32_t)block);
+  if (ev0) HIPCHK(hipEventRecord(ev0, stream), "hipEventRecord");
+  if (grid > 0) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, stream, a);
+    HIPCHK(hipGetLastError(), what);
+  }
+  if (ev1) HIPCHK(hipEventRecord(ev1, stream), "hipEventRecord");
+  return RTW_OK;
 }
 
 // A batch size (knob RTW_BATCH) as the kernels take it: within [64, 65536] and rounded down to a multiple of 64.
@@ -335,16 +351,35 @@ static RenderArgs frame_args(const DeviceCopy& c, const Frame& f, const TileSet&
   return a;
 }
 
+// The BVH walk's launch tuning of variant k on `grid` resident workgroups: what a render's path kernel and a query's
+// hit kernel share (trace_run)
+struct WalkTuning {
+  uint32_t leaf16, spill_depth, spill_lanes;
+};
+static WalkTuning tune_walk(const Knobs& kn, const Flat& flat, const KernelCfg& k, int grid) {
+  WalkTuning t;
+  // test postponed leaves once leaf16/16 of the wave's lanes hold one and cannot descend (trace_run); knob
+  // RTW_LEAF16 (1..16).  The sorted-push walk of the LDS-node kernels parks fewer leaves early: 5/16 measured best
+  // on jumpy-balls (+0.5% over 3; profiles/r02/experiments, n5)
+  const bool ldsn_spheres = k.lds_nodes() && flat.features == (flat.features & F_SPHERES);
+  t.leaf16 = (uint32_t)std::min(16, std::max(1, kn.leaf16.get(ldsn_spheres ? 5 : 3)));
+  // the LDS-node variants walk 16-bit codes within their own stack rows (pick_kernel checked
+  // stack_need4 against them) and have no HBM spill path
+  const uint32_t lds = (uint32_t)k.stack;
+  t.spill_depth = (!k.lds_nodes() && flat.stack_need > lds) ? flat.stack_need - lds : 0;
+  t.spill_lanes = (uint32_t)grid * (uint32_t)k.blk;
+  return t;
+}
+
 // enqueue_render, part 2: the launch tuning of variant k on `grid` resident workgroups, into a.  a.batch is the
 // full-frame value: pass_batch shrinks it for a small pass.
 static void tune_launch(RenderArgs& a, const Knobs& kn, const Flat& flat, const KernelCfg& k, int grid) {
   // see trace_run (measured best of 4..16 on jumpy-balls); tuning knob RTW_QUOTA16 (1..16)
   a.quota16 = (uint32_t)std::min(16, std::max(1, kn.quota16.get(12)));
-  // test postponed leaves once leaf16/16 of the wave's lanes hold one and cannot descend (trace_run); knob
-  // RTW_LEAF16 (1..16).  The sorted-push walk of the LDS-node kernels parks fewer leaves early: 5/16 measured best
-  // on jumpy-balls (+0.5% over 3; profiles/r02/experiments, n5)
-  const bool ldsn_spheres = k.lds_nodes() && flat.features == (flat.features & F_SPHERES);
-  a.leaf16 = (uint32_t)std::min(16, std::max(1, kn.leaf16.get(ldsn_spheres ? 5 : 3)));
+  const WalkTuning t = tune_walk(kn, flat, k, grid);
+  a.leaf16 = t.leaf16;
+  a.spill_depth = t.spill_depth;
+  a.spill_lanes = t.spill_lanes;
   // whole wave-loads of ids only (batch_ids): the start ring makes 64 path starts from 64 consecutive ids of a batch.
   // The 1024-lane LDS-node kernel and the BVH-less list kernels: 1024 ids per atomic (a shorter end-of-frame
   // tail; jumpy-1080p +1.2%, cornell-800 +0.5% over 2048, profiles/r03/experiments k3 / k4); the mesh
@@ -363,11 +398,6 @@ static void tune_launch(RenderArgs& a, const Knobs& kn, const Flat& flat, const 
   const bool boxed = (flat.features & ~F_SMOKE) == 0;
   const int regen_dflt = k.ldsn_ring() ? REGEN_RING_LDSN : (k.sring() ? REGEN_RING : (boxed ? 8 : 24));
   a.regen_min = (uint32_t)std::min(64, std::max(1, kn.regen_min.get(regen_dflt)));
-  // the LDS-node variants walk 16-bit codes within their own stack rows (pick_kernel checked
-  // stack_need4 against them) and have no HBM spill path
-  const uint32_t lds = (uint32_t)k.stack;
-  a.spill_depth = (!k.lds_nodes() && flat.stack_need > lds) ? flat.stack_need - lds : 0;
-  a.spill_lanes = (uint32_t)grid * (uint32_t)k.blk;
 }
 
 // Small frames: fewer ids per atomic, halving until every resident wave can take >= 32 batches.  configs[0]
@@ -397,7 +427,8 @@ static int run_passes(Scene& sc, DeviceCopy& c, RenderArgs& a, const Knobs& kn, 
   a.sbuf = static_cast<float*>(c.sbuf.p);
   const Variant var = path_kernel_variant(sc.flat, kn);
   const KernelCfg& k = var.cfg;
-  const int grid = resident_grid(c, var, count, kn.verbose);
+  const int grid = resident_blocks(c, count ? GRID_PATH_COUNT : GRID_PATH, (const void*)var.fn[count], k.blk,
+                                   "path kernel", kn.verbose);
   tune_launch(a, kn, sc.flat, k, grid);
   // (first render of a deep tree only)
   if (int e = grow(c.spill, (size_t)a.spill_depth * a.spill_lanes * sizeof(int32_t))) return e;
@@ -430,11 +461,8 @@ int enqueue_render(Scene& sc, DeviceCopy& c, const Frame& f, const TileSet& ts, 
                    uint32_t flags, hipEvent_t ev0, hipEvent_t ev1) {
   // an earlier render on this device (one the caller did not wait on) tripped the guard: report it now
   if (int e = check_guard(c)) return e;
-  if (f.w > 65536u || f.h > 65536u)
-    return fail(RTW_EINVAL, "image %ux%u: at most 65536 x 65536 (16-bit pixel coordinates in the path key)", f.w, f.h);
-  if (f.cam->time0 < sc.flat.time_lo || f.cam->time1 > sc.flat.time_hi)
-    return fail(RTW_EINVAL, "camera shutter [%g, %g) outside the committed motion range [%g, %g]",
-                f.cam->time0, f.cam->time1, sc.flat.time_lo, sc.flat.time_hi);
+  if (int e = check_image_max(f.w, f.h)) return e;
+  if (int e = check_shutter(*f.cam, sc.flat)) return e;
   RenderArgs a = frame_args(c, f, ts, d_out);
   const Knobs kn = read_knobs();
   HIPCHK(hipMemsetAsync(c.counters, 0, COUNTER_WORDS * sizeof(unsigned long long), stream), "hipMemsetAsync");
@@ -450,26 +478,14 @@ int enqueue_render(Scene& sc, DeviceCopy& c, const Frame& f, const TileSet& ts, 
 }
 
 // Ray queries (rtw_hit_rays*): the scene's variant as its renders pick it, the query kernel's own resident capacity
-// as the largest grid, and the walk's launch tuning (leaf16, the spill split) from tune_launch.
+// as the largest grid, and the walk's launch tuning (leaf16, the spill split) as a render's.
 int enqueue_hit_rays(Scene& sc, DeviceCopy& c, uint64_t n, const void* d_rays, void* d_hits, hipStream_t stream,
                      hipEvent_t ev0, hipEvent_t ev1) {
   const Knobs kn = read_knobs();
   const Variant var = path_kernel_variant(sc.flat, kn);
   const KernelCfg& k = var.cfg;
-  if (c.hit_grid <= 0 || c.hit_grid_fn != (const void*)var.hit) {
-    int per_cu = 0, cus = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, var.hit, k.blk, 0);
-    if (e != hipSuccess || per_cu < 1) per_cu = 1;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.phys) != hipSuccess || cus < 1) cus = 256;
-    c.hit_grid = per_cu * cus;
-    c.hit_grid_fn = (const void*)var.hit;
-    if (kn.verbose)
-      fprintf(stderr, "rtw: query kernel %p: block %d, %d resident blocks per CU x %d CUs\n", (void*)var.hit, k.blk,
-              per_cu, cus);
-  }
-  RenderArgs t;
-  memset(&t, 0, sizeof t);
-  tune_launch(t, kn, sc.flat, k, c.hit_grid);
+  const int resident = resident_blocks(c, GRID_HIT, (const void*)var.hit, k.blk, "query kernel", kn.verbose);
+  const WalkTuning t = tune_walk(kn, sc.flat, k, resident);
   if (int e = grow(c.spill, (size_t)t.spill_depth * t.spill_lanes * sizeof(int32_t))) return e;
   QueryArgs a;
   memset(&a, 0, sizeof a);
@@ -483,32 +499,7 @@ int enqueue_hit_rays(Scene& sc, DeviceCopy& c, uint64_t n, const void* d_rays, v
   a.spill_lanes = t.spill_lanes;
   a.spill = static_cast<int32_t*>(c.spill.p);
   a.err = c.err_host;
-  const uint64_t blocks = (n + (uint32_t)k.blk - 1u) / (uint32_t)k.blk;
-  const int grid = (int)std::min<uint64_t>((uint64_t)c.hit_grid, blocks);
-  if (ev0) HIPCHK(hipEventRecord(ev0, stream), "hipEventRecord");
-  if (grid > 0) {
-    hipLaunchKernelGGL(var.hit, dim3(grid), dim3(k.blk), 0, stream, a);
-    HIPCHK(hipGetLastError(), "hit_kernel launch");
-  }
-  if (ev1) HIPCHK(hipEventRecord(ev1, stream), "hipEventRecord");
-  return RTW_OK;
-}
-
-// The record-streaming kernels' grid: 256-lane blocks, at most the kernel's resident capacity (grid-stride beyond it)
-static int shade_grid(DeviceCopy& c, int which, const void* fn, uint64_t n, bool verbose) {
-  int& g = c.shade_grid[which];
-  if (g <= 0) {
-    int per_cu = 0, cus = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, dev::SHADE_BLOCK, 0);
-    if (e != hipSuccess || per_cu < 1) per_cu = 1;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.phys) != hipSuccess || cus < 1) cus = 256;
-    g = per_cu * cus;
-    if (verbose)
-      fprintf(stderr, "rtw: %s: block %d, %d resident blocks per CU x %d CUs\n",
-              which ? "camera_rays_kernel" : "scatter_kernel", dev::SHADE_BLOCK, per_cu, cus);
-  }
-  const uint64_t blocks = (n + (uint32_t)dev::SHADE_BLOCK - 1u) / (uint32_t)dev::SHADE_BLOCK;
-  return (int)std::min<uint64_t>((uint64_t)g, blocks);
+  return launch_query(var.hit, "hit_kernel launch", resident, k.blk, n, a, stream, ev0, ev1);
 }
 
 // Scatter queries (rtw_scatter_rays*): the scene's tables, the per-material shading records and the record arrays.
@@ -526,14 +517,9 @@ int enqueue_scatter_rays(Scene& sc, DeviceCopy& c, uint64_t n, const void* d_ray
   a.out_rays = d_out_rays;
   a.out_scatter = d_out_scatter;
   a.n = n;
-  const int grid = shade_grid(c, 0, (const void*)dev::scatter_kernel, n, kn.verbose);
-  if (ev0) HIPCHK(hipEventRecord(ev0, stream), "hipEventRecord");
-  if (grid > 0) {
-    hipLaunchKernelGGL(dev::scatter_kernel, dim3(grid), dim3(dev::SHADE_BLOCK), 0, stream, a);
-    HIPCHK(hipGetLastError(), "scatter_kernel launch");
-  }
-  if (ev1) HIPCHK(hipEventRecord(ev1, stream), "hipEventRecord");
-  return RTW_OK;
+  const int resident = resident_blocks(c, GRID_SCATTER, (const void*)dev::scatter_kernel, dev::SHADE_BLOCK,
+                                       "scatter_kernel", kn.verbose);
+  return launch_query(dev::scatter_kernel, "scatter_kernel launch", resident, dev::SHADE_BLOCK, n, a, stream, ev0, ev1);
 }
 
 // Camera-ray queries (rtw_camera_rays*): start_path's operands as frame_args computes them for a render of the frame.
@@ -552,14 +538,10 @@ int enqueue_camera_rays(DeviceCopy& c, const Frame& f, uint64_t first, uint64_t 
   a.first = first;
   a.n = n;
   a.rays = d_rays;
-  const int grid = shade_grid(c, 1, (const void*)dev::camera_rays_kernel, n, kn.verbose);
-  if (ev0) HIPCHK(hipEventRecord(ev0, stream), "hipEventRecord");
-  if (grid > 0) {
-    hipLaunchKernelGGL(dev::camera_rays_kernel, dim3(grid), dim3(dev::SHADE_BLOCK), 0, stream, a);
-    HIPCHK(hipGetLastError(), "camera_rays_kernel launch");
-  }
-  if (ev1) HIPCHK(hipEventRecord(ev1, stream), "hipEventRecord");
-  return RTW_OK;
+  const int resident = resident_blocks(c, GRID_CAMERA, (const void*)dev::camera_rays_kernel, dev::SHADE_BLOCK,
+                                       "camera_rays_kernel", kn.verbose);
+  return launch_query(dev::camera_rays_kernel, "camera_rays_kernel launch", resident, dev::SHADE_BLOCK, n, a, stream,
+                      ev0, ev1);
 }
 
 int enqueue_unpack(uint32_t w, uint32_t h, const uint32_t* d_tiles, uint32_t n_tiles, const float* d_packed,

@@ -1,8 +1,9 @@
 // rtw_render.cpp — the host render runtime behind the C-ABI's device half: the scene's device copies (upload, release,
-// the grow-only buffers), the render calls' shared opening (check_frame, need_copy), statistics, the traversal guard's
-// error word, and the render / ray-query / status entry points of one device.  Plain HIP runtime API: the kernels, which
-// variant a scene runs and how a render or a query is enqueued are rtw_kernel.hip's (enqueue_render, enqueue_hit_rays,
-// enqueue_scatter_rays, enqueue_camera_rays, enqueue_unpack); the render over several devices is rtw_multi.cpp's.
+// the grow-only buffers), the render calls' shared opening (check_frame, need_copy) and the frame checks it shares with
+// the camera-ray calls, statistics, the traversal guard's error word, and the render / status / diagnostic entry points
+// of one device.  Plain HIP runtime API: the kernels, which variant a scene runs and how a render is enqueued are
+// rtw_kernel.hip's (enqueue_render, enqueue_unpack); the six ray-query calls are rtw_query.cpp's, the render over
+// several devices rtw_multi.cpp's.
 #include <math.h>
 #include <string.h>
 
@@ -140,7 +141,24 @@ int grow(DevBuf& b, size_t bytes) {
 int check_frame(const rtw_scene* s, const Frame& f, bool out) {
   if (!s || !f.cam || !f.bg || !out) return fail(RTW_EINVAL, "NULL argument");
   if (!s->s.committed) return fail(RTW_ESTATE, "scene not committed");
-  if (f.w < 2 || f.h < 2) return fail(RTW_EINVAL, "image must be at least 2x2 (lib.rs:84-85 divides by w-1, h-1)");
+  return check_image_min(f.w, f.h);
+}
+
+int check_image_min(uint32_t w, uint32_t h) {
+  if (w < 2 || h < 2) return fail(RTW_EINVAL, "image must be at least 2x2 (lib.rs:84-85 divides by w-1, h-1)");
+  return RTW_OK;
+}
+
+int check_image_max(uint32_t w, uint32_t h) {
+  if (w > 65536u || h > 65536u)
+    return fail(RTW_EINVAL, "image %ux%u: at most 65536 x 65536 (16-bit pixel coordinates in the path key)", w, h);
+  return RTW_OK;
+}
+
+int check_shutter(const rtw_camera& cam, const Flat& f) {
+  if (cam.time0 < f.time_lo || cam.time1 > f.time_hi)
+    return fail(RTW_EINVAL, "camera shutter [%g, %g) outside the committed motion range [%g, %g]", cam.time0, cam.time1,
+                f.time_lo, f.time_hi);
   return RTW_OK;
 }
 
@@ -276,259 +294,6 @@ int rtw_render_device_strided(rtw_scene* s, int device, const rtw_camera* cam, c
                 (unsigned long long)nt);
   const TileSet ts{nullptr, first_tile, tile_stride, n_tiles, true};
   return render_device(s, device, f, ts, d_out, abi_stream(stream), flags, stats);
-}
-
-// rtw_hit_rays and rtw_hit_rays_device: the checks they share, in the render calls' order (a NULL argument, then the
-// scene's state).  The state asked for is a flattened scene, so that a commit that found no device answers RTW_ENODEV.
-static int hit_rays_check(const rtw_scene* s, uint64_t n, const void* rays, const void* hits) {
-  if (!s || (n && (!rays || !hits))) return fail(RTW_EINVAL, "NULL argument");
-  if (!s->s.flattened) return fail(RTW_ESTATE, "scene not committed");
-  return RTW_OK;
-}
-
-int rtw_hit_rays(rtw_scene* s, int device, uint64_t n, const void* rays, void* hits, rtw_stats* stats) {
-  auto t0 = std::chrono::steady_clock::now();
-  if (int e = hit_rays_check(s, n, rays, hits)) return e;
-  rtw_stats st{};
-  if (n == 0) {
-    if (stats) *stats = st;
-    return RTW_OK;
-  }
-  const rtw_ray* r = static_cast<const rtw_ray*>(rays);
-  const float lo = s->s.flat.time_lo, hi = s->s.flat.time_hi;
-  for (uint64_t k = 0; k < n; ++k)
-    if (!(r[k].time >= lo && r[k].time <= hi))
-      return fail(RTW_EINVAL, "ray %llu: time %g outside the committed motion range [%g, %g]", (unsigned long long)k,
-                  r[k].time, lo, hi);
-  DeviceCopy* c = need_copy(s->s, device, device < 0 ? nullptr : "");
-  if (!c) return RTW_ENODEV;
-  DeviceGuard g;
-  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
-  if (int e = check_guard(*c)) return e;
-  if (int e = copy_events(*c)) return e;
-  constexpr uint64_t CHUNK = 1ull << 20;
-  const uint64_t cap = std::min(n, CHUNK);
-  if (int e = grow(c->qrays, cap * sizeof(rtw_ray))) return e;
-  if (int e = grow(c->qhits, cap * sizeof(rtw_hit))) return e;
-  rtw_hit* out = static_cast<rtw_hit*>(hits);
-  for (uint64_t k = 0; k < n; k += CHUNK) {
-    const uint64_t m = std::min(CHUNK, n - k);
-    HIPCHK(hipMemcpy(c->qrays.p, r + k, m * sizeof(rtw_ray), hipMemcpyHostToDevice), "hipMemcpy(rays)");
-    if (int e = enqueue_hit_rays(s->s, *c, m, c->qrays.p, c->qhits.p, nullptr, c->ev[0], c->ev[1])) return e;
-    HIPCHK(hipMemcpy(out + k, c->qhits.p, m * sizeof(rtw_hit), hipMemcpyDeviceToHost), "hipMemcpy(hits)");
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]), "hipEventElapsedTime");
-    st.kernel_ms += ms;
-    if (int e = check_guard(*c)) return e;
-  }
-  st.rays = n;
-  st.total_ms = ms_since(t0);
-  if (stats) *stats = st;
-  return RTW_OK;
-}
-
-int rtw_hit_rays_device(rtw_scene* s, int device, uint64_t n, const void* d_rays, void* d_hits, void* stream,
-                        rtw_stats* stats) {
-  auto t0 = std::chrono::steady_clock::now();
-  if (int e = hit_rays_check(s, n, d_rays, d_hits)) return e;
-  rtw_stats st{};
-  if (n == 0) {
-    if (stats) *stats = st;
-    return RTW_OK;
-  }
-  if (((uintptr_t)d_rays | (uintptr_t)d_hits) & 15u) return fail(RTW_EINVAL, "d_rays and d_hits must be 16-byte aligned");
-  DeviceCopy* c = need_copy(s->s, device, device < 0 ? nullptr : "");
-  if (!c) return RTW_ENODEV;
-  DeviceGuard g;
-  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
-  if (int e = check_guard(*c)) return e;
-  if (stats)
-    if (int e = copy_events(*c)) return e;
-  const hipEvent_t e0 = stats ? c->ev[0] : nullptr, e1 = stats ? c->ev[1] : nullptr;
-  const hipStream_t st_ = abi_stream(stream);
-  if (int e = enqueue_hit_rays(s->s, *c, n, d_rays, d_hits, st_, e0, e1)) return e;
-  if (stats) {
-    HIPCHK(hipStreamSynchronize(st_), "hit_kernel");
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime");
-    if (int e = check_guard(*c)) return e;
-    st.rays = n;
-    st.kernel_ms = ms;
-    st.total_ms = ms_since(t0);
-    *stats = st;
-  }
-  return RTW_OK;
-}
-
-// rtw_camera_rays and rtw_camera_rays_device: hit_rays_check (the camera as its first array), then the frame and the
-// shutter as the render calls check them (check_frame, enqueue_render) and the path range.  Host only.
-static int camera_rays_check(const rtw_scene* s, const rtw_camera* cam, uint32_t w, uint32_t h, uint32_t spp,
-                             uint64_t first, uint64_t n, const void* rays) {
-  if (!s || !cam || (n && !rays)) return fail(RTW_EINVAL, "NULL argument");
-  if (int e = hit_rays_check(s, n, cam, rays)) return e;
-  if (w < 2 || h < 2) return fail(RTW_EINVAL, "image must be at least 2x2 (lib.rs:84-85 divides by w-1, h-1)");
-  if (w > 65536u || h > 65536u)
-    return fail(RTW_EINVAL, "image %ux%u: at most 65536 x 65536 (16-bit pixel coordinates in the path key)", w, h);
-  const uint64_t paths = (uint64_t)w * h * spp;  // < 2^64: w * h <= 2^32
-  if (first > paths || n > paths - first)
-    return fail(RTW_EINVAL, "paths [%llu, %llu + %llu) leave the frame's %llu", (unsigned long long)first,
-                (unsigned long long)first, (unsigned long long)n, (unsigned long long)paths);
-  if (cam->time0 < s->s.flat.time_lo || cam->time1 > s->s.flat.time_hi)
-    return fail(RTW_EINVAL, "camera shutter [%g, %g) outside the committed motion range [%g, %g]", cam->time0,
-                cam->time1, s->s.flat.time_lo, s->s.flat.time_hi);
-  // (a camera filled in by hand: the time draw's retry loop ends only for a non-empty range; camera.rs:72 panics)
-  if (!(cam->time0 < cam->time1)) return fail(RTW_EINVAL, "camera shutter [%g, %g) is empty", cam->time0, cam->time1);
-  return RTW_OK;
-}
-
-int rtw_camera_rays(rtw_scene* s, int device, const rtw_camera* cam, uint32_t w, uint32_t h, uint32_t spp,
-                    uint64_t seed, uint64_t first, uint64_t n, void* rays, rtw_stats* stats) {
-  auto t0 = std::chrono::steady_clock::now();
-  if (int e = camera_rays_check(s, cam, w, h, spp, first, n, rays)) return e;
-  rtw_stats st{};
-  if (n == 0) {
-    if (stats) *stats = st;
-    return RTW_OK;
-  }
-  DeviceCopy* c = need_copy(s->s, device, device < 0 ? nullptr : "");
-  if (!c) return RTW_ENODEV;
-  DeviceGuard g;
-  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
-  if (int e = copy_events(*c)) return e;
-  constexpr uint64_t CHUNK = 1ull << 20;
-  if (int e = grow(c->qrays, std::min(n, CHUNK) * sizeof(rtw_ray))) return e;
-  const float no_bg[3] = {0.f, 0.f, 0.f};
-  const Frame f{cam, no_bg, w, h, spp, 0, seed};
-  rtw_ray* out = static_cast<rtw_ray*>(rays);
-  for (uint64_t k = 0; k < n; k += CHUNK) {
-    const uint64_t m = std::min(CHUNK, n - k);
-    if (int e = enqueue_camera_rays(*c, f, first + k, m, c->qrays.p, nullptr, c->ev[0], c->ev[1])) return e;
-    HIPCHK(hipMemcpy(out + k, c->qrays.p, m * sizeof(rtw_ray), hipMemcpyDeviceToHost), "hipMemcpy(rays)");
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]), "hipEventElapsedTime");
-    st.kernel_ms += ms;
-  }
-  st.total_ms = ms_since(t0);
-  if (stats) *stats = st;
-  return RTW_OK;
-}
-
-int rtw_camera_rays_device(rtw_scene* s, int device, const rtw_camera* cam, uint32_t w, uint32_t h, uint32_t spp,
-                           uint64_t seed, uint64_t first, uint64_t n, void* d_rays, void* stream, rtw_stats* stats) {
-  auto t0 = std::chrono::steady_clock::now();
-  if (int e = camera_rays_check(s, cam, w, h, spp, first, n, d_rays)) return e;
-  rtw_stats st{};
-  if (n == 0) {
-    if (stats) *stats = st;
-    return RTW_OK;
-  }
-  if ((uintptr_t)d_rays & 15u) return fail(RTW_EINVAL, "d_rays must be 16-byte aligned");
-  DeviceCopy* c = need_copy(s->s, device, device < 0 ? nullptr : "");
-  if (!c) return RTW_ENODEV;
-  DeviceGuard g;
-  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
-  if (stats)
-    if (int e = copy_events(*c)) return e;
-  const hipEvent_t e0 = stats ? c->ev[0] : nullptr, e1 = stats ? c->ev[1] : nullptr;
-  const hipStream_t st_ = abi_stream(stream);
-  const float no_bg[3] = {0.f, 0.f, 0.f};
-  const Frame f{cam, no_bg, w, h, spp, 0, seed};
-  if (int e = enqueue_camera_rays(*c, f, first, n, d_rays, st_, e0, e1)) return e;
-  if (stats) {
-    HIPCHK(hipStreamSynchronize(st_), "camera_rays_kernel");
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime");
-    st.kernel_ms = ms;
-    st.total_ms = ms_since(t0);
-    *stats = st;
-  }
-  return RTW_OK;
-}
-
-// rtw_scatter_rays and rtw_scatter_rays_device: hit_rays_check over all five arrays
-static int scatter_rays_check(const rtw_scene* s, uint64_t n, const void* rays, const void* hits, const float* bg,
-                              const void* out_rays, const void* out_scatter) {
-  if (!s || !bg || (n && (!rays || !hits || !out_rays || !out_scatter))) return fail(RTW_EINVAL, "NULL argument");
-  return hit_rays_check(s, n, rays, hits);
-}
-
-int rtw_scatter_rays(rtw_scene* s, int device, uint64_t n, const void* rays, const void* hits,
-                     const float background[3], void* out_rays, void* out_scatter, rtw_stats* stats) {
-  auto t0 = std::chrono::steady_clock::now();
-  if (int e = scatter_rays_check(s, n, rays, hits, background, out_rays, out_scatter)) return e;
-  rtw_stats st{};
-  if (n == 0) {
-    if (stats) *stats = st;
-    return RTW_OK;
-  }
-  const rtw_ray* r = static_cast<const rtw_ray*>(rays);
-  for (uint64_t k = 0; k < n; ++k)
-    if (r[k].stream == 0)
-      return fail(RTW_EINVAL, "record %llu: stream word 0 (the generator never leaves that state)",
-                  (unsigned long long)k);
-  DeviceCopy* c = need_copy(s->s, device, device < 0 ? nullptr : "");
-  if (!c) return RTW_ENODEV;
-  DeviceGuard g;
-  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
-  if (int e = copy_events(*c)) return e;
-  constexpr uint64_t CHUNK = 1ull << 20;
-  const uint64_t cap = std::min(n, CHUNK);
-  if (int e = grow(c->qrays, cap * sizeof(rtw_ray))) return e;
-  if (int e = grow(c->qhits, cap * sizeof(rtw_hit))) return e;
-  if (int e = grow(c->qscatter, cap * sizeof(rtw_scatter))) return e;
-  const rtw_hit* hr = static_cast<const rtw_hit*>(hits);
-  rtw_ray* out_r = static_cast<rtw_ray*>(out_rays);
-  rtw_scatter* out_s = static_cast<rtw_scatter*>(out_scatter);
-  for (uint64_t k = 0; k < n; k += CHUNK) {
-    const uint64_t m = std::min(CHUNK, n - k);
-    HIPCHK(hipMemcpy(c->qrays.p, r + k, m * sizeof(rtw_ray), hipMemcpyHostToDevice), "hipMemcpy(rays)");
-    HIPCHK(hipMemcpy(c->qhits.p, hr + k, m * sizeof(rtw_hit), hipMemcpyHostToDevice), "hipMemcpy(hits)");
-    // in place on the device: the staged rays become the scattered rays
-    if (int e = enqueue_scatter_rays(s->s, *c, m, c->qrays.p, c->qhits.p, background, c->qrays.p, c->qscatter.p, nullptr,
-                                     c->ev[0], c->ev[1]))
-      return e;
-    HIPCHK(hipMemcpy(out_r + k, c->qrays.p, m * sizeof(rtw_ray), hipMemcpyDeviceToHost), "hipMemcpy(out rays)");
-    HIPCHK(hipMemcpy(out_s + k, c->qscatter.p, m * sizeof(rtw_scatter), hipMemcpyDeviceToHost), "hipMemcpy(scatter)");
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]), "hipEventElapsedTime");
-    st.kernel_ms += ms;
-  }
-  st.total_ms = ms_since(t0);
-  if (stats) *stats = st;
-  return RTW_OK;
-}
-
-int rtw_scatter_rays_device(rtw_scene* s, int device, uint64_t n, const void* d_rays, const void* d_hits,
-                            const float background[3], void* d_out_rays, void* d_out_scatter, void* stream,
-                            rtw_stats* stats) {
-  auto t0 = std::chrono::steady_clock::now();
-  if (int e = scatter_rays_check(s, n, d_rays, d_hits, background, d_out_rays, d_out_scatter)) return e;
-  rtw_stats st{};
-  if (n == 0) {
-    if (stats) *stats = st;
-    return RTW_OK;
-  }
-  if (((uintptr_t)d_rays | (uintptr_t)d_hits | (uintptr_t)d_out_rays | (uintptr_t)d_out_scatter) & 15u)
-    return fail(RTW_EINVAL, "d_rays, d_hits, d_out_rays and d_out_scatter must be 16-byte aligned");
-  DeviceCopy* c = need_copy(s->s, device, device < 0 ? nullptr : "");
-  if (!c) return RTW_ENODEV;
-  DeviceGuard g;
-  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
-  if (stats)
-    if (int e = copy_events(*c)) return e;
-  const hipEvent_t e0 = stats ? c->ev[0] : nullptr, e1 = stats ? c->ev[1] : nullptr;
-  const hipStream_t st_ = abi_stream(stream);
-  if (int e = enqueue_scatter_rays(s->s, *c, n, d_rays, d_hits, background, d_out_rays, d_out_scatter, st_, e0, e1))
-    return e;
-  if (stats) {
-    HIPCHK(hipStreamSynchronize(st_), "scatter_kernel");
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime");
-    st.kernel_ms = ms;
-    st.total_ms = ms_since(t0);
-    *stats = st;
-  }
-  return RTW_OK;
 }
 
 int rtw_render_status(rtw_scene* s, int device) {

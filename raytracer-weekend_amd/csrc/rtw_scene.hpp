@@ -3,7 +3,8 @@
 // The graph keeps the reference's Hittable tree shape (raytracer_weekend_lib/src/hittable/,
 // bvh.rs) so that rtw_scene_dump() can hand the exact hierarchy to the test oracle; the
 // flattener (rtw_flatten.cpp) turns it into the device layout of rtw_device.hpp.  Below it: the scene's device
-// copies, and what the host sources that call HIP share (the check macro, the device guard, Frame, TileSet).
+// copies, and what the host sources that call HIP share (the check macro, the device guard, Frame, TileSet, the frame
+// checks of the render and camera-ray calls) -- rtw_render.cpp, rtw_query.cpp, rtw_multi.cpp and rtw_kernel.hip.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -95,6 +96,14 @@ struct DevBuf {  // a grow-only device allocation
   size_t cap = 0;
 };
 
+// A kernel's resident capacity on a device (blocks per CU x CUs), kept for the kernel it was computed for: knobs may
+// switch a scene's variant between calls (rtw_kernel.hip resident_blocks)
+struct ResidentGrid {
+  const void* fn = nullptr;
+  int blocks = 0;
+};
+enum GridSlot { GRID_PATH, GRID_PATH_COUNT, GRID_HIT, GRID_SCATTER, GRID_CAMERA, GRID_SLOTS };
+
 struct DeviceCopy {
   int device = -1;  // the logical device the caller names (rtw_render_device, rtw_render_multi's device d)
   int phys = -1;    // the HIP device it lives on: = device, except under rtw_diag_alias_devices (all on 0)
@@ -109,17 +118,13 @@ struct DeviceCopy {
   DevBuf spill;                            // traversal-stack overflow (trees deeper than the LDS stack)
   hipEvent_t kev[64][2] = {};              // pairs around path-kernel launches (ring, rtw_path_kernel_times)
   uint32_t kev_head = 0, kev_count = 0;
-  int grid[2] = {0, 0};                    // resident path_kernel grid (plain, counting) of the
-  const void* grid_fn[2] = {nullptr, nullptr};  // variant it was computed for (knobs may switch variants)
+  ResidentGrid grids[GRID_SLOTS];          // the path kernel (plain, counting) and the three query kernels
   // device buffers kept across render calls (grown, never shrunk; freed by release()): a
   // 30-camera animation through rtw_render does no hipMalloc after the first frame
   DevBuf image, tiles, packed, gathered, gather_ids;
   DevBuf qrays, qhits;                     // rtw_hit_rays' staging: one chunk of rays and of records
-  int hit_grid = 0;                        // resident hit_kernel grid of the
-  const void* hit_grid_fn = nullptr;       // variant it was computed for
   DevBuf mshade;                           // Flat::mshade (uploaded with the scene; scatter_kernel's material table)
   DevBuf qscatter;                         // rtw_scatter_rays' staging: one chunk of rtw_scatter records
-  int shade_grid[2] = {0, 0};              // resident grids of scatter_kernel and camera_rays_kernel
   hipEvent_t ev[2] = {nullptr, nullptr};   // pair timing rtw_render / multi calls (copy_events)
   hipStream_t stream = nullptr;            // rtw_render_multi's stream on this device
   hipEvent_t gev[2] = {nullptr, nullptr};  // pair around rtw_render_multi's gather (device 0)
@@ -153,7 +158,7 @@ int fail(int code, const char* fmt, ...);
 // the gate is ignored with one warning on stderr (rtw_capi.cpp).
 const char* tuning_env(const char* name);
 
-// ---- small things every HIP-calling source shares (rtw_render.cpp, rtw_multi.cpp, rtw_kernel.hip)
+// ---- small things every HIP-calling source shares (rtw_render.cpp, rtw_query.cpp, rtw_multi.cpp, rtw_kernel.hip)
 #define HIPCHK(x, what)                                                                        \
   do {                                                                                         \
     hipError_t e_ = (x);                                                                       \
@@ -206,6 +211,12 @@ int grow(DevBuf& b, size_t bytes);            // current device; contents not ke
 // The render calls' argument checks, in this order: a NULL argument (RTW_EINVAL), an uncommitted scene (RTW_ESTATE),
 // an image under 2x2 (RTW_EINVAL).  `out` is the call's image, device pointer or sink.
 int check_frame(const rtw_scene* s, const Frame& f, bool out);
+// The frame checks one by one, each RTW_EINVAL, shared by the render calls (check_frame; enqueue_render, after the
+// device copy is found) and rtw_camera_rays*: an image under 2x2, a side over 65536, a shutter that leaves the
+// committed motion range
+int check_image_min(uint32_t w, uint32_t h);
+int check_image_max(uint32_t w, uint32_t h);
+int check_shutter(const rtw_camera& cam, const Flat& f);
 // find_copy, or NULL with RTW_ENODEV set: "not committed to device <device><hint>", or without a hint (the calls
 // that name no device) "no device copy"
 DeviceCopy* need_copy(Scene& s, int device, const char* hint = "");
@@ -232,7 +243,7 @@ int enqueue_hit_rays(Scene& s, DeviceCopy& c, uint64_t n, const void* d_rays, vo
 int enqueue_scatter_rays(Scene& s, DeviceCopy& c, uint64_t n, const void* d_rays, const void* d_hits, const float* bg,
                          void* d_out_rays, void* d_out_scatter, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1);
 // enqueue the camera rays of paths [first, first + n) of frame f (its max_depth and bg unused) into d_rays, likewise;
-// the caller has checked the frame and the shutter (rtw_render.cpp camera_rays_check)
+// the caller has checked the frame and the shutter (rtw_query.cpp camera_rays_check)
 int enqueue_camera_rays(DeviceCopy& c, const Frame& f, uint64_t first, uint64_t n, void* d_rays, hipStream_t stream,
                         hipEvent_t ev0, hipEvent_t ev1);
 int enqueue_unpack(uint32_t w, uint32_t h, const uint32_t* d_tiles, uint32_t n_tiles, const float* d_packed,

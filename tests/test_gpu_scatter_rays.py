@@ -363,3 +363,22 @@ def test_second_staging_chunk(gpu, orc, mat_scene):
         assert len(tail) > 65 and (tail == a[:len(tail)]).all(), "the last, partial copy (across the chunk boundary)"
     _same_records(sc[:nb], want_s, "first copy")
     _same_records(out[:nb][slot != 4], want_r[slot != 4], "first copy: out rays")
+
+
+def test_camera_rays_second_staging_chunk(gpu):
+    """2^20 + 65 paths from path 7 through the host form (two staging chunks; the second starts at first + 2^20) equal
+    one rtw_camera_rays_device call for the range: a single launch without staging, of the kernel that
+    test_camera_rays_match_the_oracle pins."""
+    import torch
+    w, h, spp, seed, first, n = 640, 410, 4, 11, 7, (1 << 20) + 65
+    assert w * h * spp >= first + n
+    s = gpu.Scene()
+    cam, _bg = s.preset("jumpy-balls", 16 / 9, seed=3)
+    s.commit(device=0)
+    got, st = s.camera_rays(cam, w, h, spp, seed, first=first, n=n, device=0, want_stats=True)
+    assert len(got) == n and st["kernel_ms"] > 0 and st["rays"] == 0
+    dev = torch.device("cuda:0")
+    d_rays = torch.zeros(n * 40, dtype=torch.uint8, device=dev)
+    s.camera_rays_device(cam, w, h, spp, seed, first, n, d_rays.data_ptr(), 0, 0)
+    torch.cuda.synchronize(dev)
+    _same_records(got, np.frombuffer(d_rays.cpu().numpy().tobytes(), gpu.RAY_DTYPE), "paths [7, 7 + 2^20 + 65)")

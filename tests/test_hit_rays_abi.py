@@ -126,6 +126,22 @@ def test_bad_time_is_einval_from_the_host_call(rtw, time):
     assert "ray 3" in msg and "motion range" in msg
 
 
+@pytest.mark.parametrize("which", ["d_rays", "d_hits"])
+def test_device_form_wants_16_byte_aligned_arrays(rtw, which):
+    """Checked on the host before the device copy is looked for, so with or without a GPU; and not at all for n = 0,
+    which looks at no array."""
+    s, _ = _world(rtw)
+    L = rtw.lib()
+    buf = np.zeros(4 * 48 + 16, np.uint8)
+    base = (buf.ctypes.data + 15) & ~15
+    ptr = {"d_rays": base, "d_hits": base}
+    ptr[which] += 8
+    args = (C.c_void_p(ptr["d_rays"]), C.c_void_p(ptr["d_hits"]), None, None)
+    assert L.rtw_hit_rays_device(s._p, 0, 3, *args) == rtw.RTW_EINVAL
+    assert "16-byte aligned" in L.rtw_last_error().decode()
+    assert L.rtw_hit_rays_device(s._p, 0, 0, *args) == 0
+
+
 def test_without_a_device_copy(rtw):
     """A scene that rtw_scene_commit flattened: RTW_ENODEV where there is no GPU (never a CPU fallback), the records
     where there is one."""

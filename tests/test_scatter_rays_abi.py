@@ -202,6 +202,29 @@ def test_camera_frame_range_and_shutter_are_checked_on_the_host(rtw, device_call
     assert _camera_call(rtw, s, _camera(rtw), device_call, w=1, n=1) == rtw.RTW_EINVAL  # lib.rs:84 divides by w - 1
 
 
+@pytest.mark.parametrize("which", ["d_rays", "d_hits", "d_out_rays", "d_out_scatter", "camera d_rays"])
+def test_device_forms_want_16_byte_aligned_arrays(rtw, which):
+    """Checked on the host before the device copy is looked for, so with or without a GPU; and not at all for n = 0,
+    which looks at no array."""
+    s, _ = _world(rtw)
+    L = rtw.lib()
+    buf = np.zeros(4 * 48 + 16, np.uint8)
+    base = (buf.ctypes.data + 15) & ~15
+    bg = np.asarray(BG, np.float32).ctypes.data_as(C.POINTER(C.c_float))
+
+    def call(n):
+        if which == "camera d_rays":
+            return L.rtw_camera_rays_device(s._p, 0, C.byref(_camera(rtw).c), W, H, SPP, 11, 0, n, C.c_void_p(base + 8),
+                                            None, None)
+        p = {k: base + (8 if k == which else 0) for k in ("d_rays", "d_hits", "d_out_rays", "d_out_scatter")}
+        return L.rtw_scatter_rays_device(s._p, 0, n, p["d_rays"], p["d_hits"], bg, p["d_out_rays"], p["d_out_scatter"],
+                                         None, None)
+
+    assert call(3) == rtw.RTW_EINVAL
+    assert "16-byte aligned" in L.rtw_last_error().decode()
+    assert call(0) == 0
+
+
 def test_without_a_device_copy(rtw):
     """A scene that rtw_scene_commit flattened: RTW_ENODEV where there is no GPU (never a CPU fallback), the records
     where there is one."""
