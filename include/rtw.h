@@ -333,7 +333,42 @@ int rtw_scatter_rays_device(rtw_scene* s, int device, uint64_t n, const void* d_
                             const float background[3], void* d_out_rays, void* d_out_scatter, void* stream,
                             rtw_stats* stats);
 
-/* Errors of renders the caller did not wait for.  A path kernel whose BVH walk trips its guard (a
+/* ---- radiance queries: Raytracer::sample_ray(&ray, rng, depth) -> Color (lib.rs:97-117) for rays the caller chooses
+ *      (custom cameras, light probes, irradiance baking, per-sample radiance for the caller's own filters), the whole
+ *      path traced on the device in one persistent launch of the scene's own path-kernel variant, with the render's
+ *      f32 operations and draw order: the records of a frame's rtw_camera_rays, summed per pixel in sample order, are
+ *      rtw_render's image bit for bit, and each record is what the rtw_hit_rays -> rtw_scatter_rays loop gives for
+ *      its ray. */
+/* lib.rs:97-117 sample_ray for a caller's ray: the render's L = T * terminal */
+typedef struct {
+  float color[3];     /* sample_ray's value, path_kernel's bits (T*0 for an absorbed / depth-exhausted path) */
+  uint32_t segments;  /* world.hit queries this path made (lib.rs:102) */
+  uint64_t stream;    /* generator state when the path ended */
+  uint32_t flags, reserved;
+} rtw_sample;         /* 32 B */
+enum { RTW_SAMPLE_END_MISS = 1, RTW_SAMPLE_END_NO_SCATTER = 2 /* light or absorbed */,
+       RTW_SAMPLE_BAD_RAY = 4, RTW_SAMPLE_END_DEPTH = 8 };
+/* n rays from host memory, blocking: `rays` is rtw_ray[n] as rtw_hit_rays takes it, `samples` receives rtw_sample[n].
+ * A ray's `stream` is the path generator's state at the first segment: the materials draw from it and it keys the media
+ * sub-streams (rtw_camera_rays' word for a camera ray).  The record's `stream` is the word rtw_scatter_rays' out ray
+ * carries at the path's last step: the last segment's own word for a miss or a light, the advanced word for an absorbed
+ * Metal ray, the last scattered ray's word when depth ran out.  max_depth = 0: colour +0, segments 0, flags 0, the
+ * stream copied through (lib.rs:98-100).  Degenerate rays are legal, as for rtw_hit_rays.  RTW_EINVAL: a NULL argument
+ * (the arrays only with n > 0); a ray whose time is NaN or outside the committed motion range, or whose stream word is
+ * 0 (a host scan before anything is enqueued); a traversal guard trip.  RTW_ESTATE / RTW_ENODEV / n = 0 / the staging
+ * (2^20 rays at a time) as rtw_hit_rays.  stats (may be NULL): rays = the sum of `segments`, counted on the device as
+ * a render counts them, paths = n, kernel_ms, total_ms. */
+int rtw_sample_rays(rtw_scene* s, int device, uint64_t n, const void* rays, const float background[3],
+                    uint32_t max_depth, void* samples, rtw_stats* stats);
+/* The same over DEVICE arrays (16-byte aligned) on the caller's `stream`; only enqueues unless stats != NULL; a pending
+ * guard trip is reported before it enqueues.  No host scan: a ray with a bad time or a zero stream word comes back with
+ * RTW_SAMPLE_BAD_RAY and every other field 0, its neighbours unaffected.  The call uses the device copy's
+ * traversal-stack spill area, its counters and its path-id queue: it must be serialised on one stream with the renders
+ * and rtw_hit_rays* queries of the same (scene, device), as they among themselves. */
+int rtw_sample_rays_device(rtw_scene* s, int device, uint64_t n, const void* d_rays, const float background[3],
+                           uint32_t max_depth, void* d_samples, void* stream, rtw_stats* stats);
+
+/* Errors of renders the caller did not wait for. A path kernel whose BVH walk trips its guard (a
  * corrupt tree: the walk is bounded, and the first trip closes the path queue, so the grid drains after
  * about one trip per wave) sets the device's host-mapped error word.  It is reported, and cleared, as
  * RTW_EINVAL by the first rtw_render* call on that device that starts after the faulting render has

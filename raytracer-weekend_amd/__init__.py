@@ -92,7 +92,15 @@ class rtw_scatter(C.Structure):  # material.rs:18-21 Scatter + Material::emitted
                 ("reserved", C.c_uint32)]
 
 
+class rtw_sample(C.Structure):  # lib.rs:97-117 sample_ray's value for a caller's ray (include/rtw.h)
+    _fields_ = [("color", C.c_float * 3), ("segments", C.c_uint32), ("stream", C.c_uint64), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 HIT_HIT, HIT_FRONT_FACE, HIT_BAD_RAY = 1, 2, 4
+SAMPLE_END_MISS, SAMPLE_END_NO_SCATTER, SAMPLE_BAD_RAY, SAMPLE_END_DEPTH = 1, 2, 4, 8
+SAMPLE_DTYPE = np.dtype([("color", np.float32, 3), ("segments", np.uint32), ("stream", np.uint64),
+                         ("flags", np.uint32), ("reserved", np.uint32)])
 SCATTER_SCATTERED, SCATTER_MISS, SCATTER_BAD = 1, 2, 4
 SCATTER_DTYPE = np.dtype([("attenuation", np.float32, 3), ("emitted", np.float32, 3), ("flags", np.uint32),
                           ("reserved", np.uint32)])
@@ -160,6 +168,10 @@ _SIGS = {
                                    C.POINTER(rtw_ray), C.POINTER(rtw_scatter), C.POINTER(rtw_stats)]),
     "rtw_scatter_rays_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, _F, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.POINTER(rtw_stats)]),
+    "rtw_sample_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(rtw_ray), _F, C.c_uint32,
+                                  C.POINTER(rtw_sample), C.POINTER(rtw_stats)]),
+    "rtw_sample_rays_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, _F, C.c_uint32, C.c_void_p,
+                                         C.c_void_p, C.POINTER(rtw_stats)]),
     "rtw_render_status": (C.c_int, [C.c_void_p, C.c_int]),
     "rtw_diag_corrupt_bvh": (C.c_int, [C.c_void_p, C.c_int]),
     "rtw_diag_alias_devices": (C.c_int, [C.c_void_p, C.c_int]),
@@ -526,6 +538,29 @@ class Scene:
                                              _fp(_fa(background)), C.c_void_p(d_out_rays_ptr),
                                              C.c_void_p(d_out_scatter_ptr), C.c_void_p(stream_ptr),
                                              C.byref(st) if want_stats else None))
+        return st.as_dict() if want_stats else None
+
+    def sample_rays(self, rays, background, max_depth: int = 50, device: int = -1, want_stats: bool = False):
+        """Raytracer::sample_ray (lib.rs:97-117) for RAY_DTYPE rays the caller chose (make_rays, camera_rays): every
+        path traced to its end on the device in one launch, with the render's arithmetic and draw order.  A ray's
+        stream word (non-zero) is its path's generator state.  -> SAMPLE_DTYPE records (color, segments, the final
+        stream word, SAMPLE_END_* flags)[, stats: rays = the segments traced, paths = n]."""
+        rays = np.ascontiguousarray(rays, RAY_DTYPE)
+        out = np.zeros(len(rays), SAMPLE_DTYPE)
+        st = rtw_stats()
+        _check(lib().rtw_sample_rays(self._p, device, len(rays), rays.ctypes.data_as(C.POINTER(rtw_ray)),
+                                     _fp(_fa(background)), max_depth, out.ctypes.data_as(C.POINTER(rtw_sample)),
+                                     C.byref(st)))
+        return (out, st.as_dict()) if want_stats else out
+
+    def sample_rays_device(self, d_rays_ptr: int, background, max_depth: int, d_samples_ptr: int, n: int,
+                           device: int = 0, stream_ptr: int = 0, want_stats: bool = False):
+        """Enqueue the same over device arrays (rtw_ray[n] -> rtw_sample[n], 16-byte aligned) on a stream, which must
+        be the one the scene's renders and hit queries run on; waits only for stats."""
+        st = rtw_stats()
+        _check(lib().rtw_sample_rays_device(self._p, device, n, C.c_void_p(d_rays_ptr), _fp(_fa(background)),
+                                            max_depth, C.c_void_p(d_samples_ptr), C.c_void_p(stream_ptr),
+                                            C.byref(st) if want_stats else None))
         return st.as_dict() if want_stats else None
 
     def render_status(self, device: int = -1) -> None:

@@ -15,6 +15,7 @@
 //   world.hit(&ray, 0.001, INFINITY) -> Option<HitRecord>  world.hit_rays(rays) -> std::vector<Hit>  hittable/mod.rs:22-69
 //   cam.get_ray(u, v, rng) per path of a frame          world.camera_rays(cam, w, h, spp, seed) -> std::vector<Ray>  camera.rs:66-74
 //   rec.material.scatter(&ray, &rec, rng) / emitted()   world.scatter_rays(rays, hits, background) -> {rays, Scatter}  material.rs:23-26
+//   raytracer.sample_ray(&ray, rng, depth) -> Color      world.sample_rays(rays, background, max_depth) -> std::vector<Sample>  lib.rs:97-117
 // Errors (the reference panics) throw rtw::Error with rtw_last_error()'s message.
 #pragma once
 #include <stdexcept>
@@ -76,6 +77,18 @@ struct Scatter {
   bool bad() const { return flags & RTW_SCATTER_BAD; }
 };
 static_assert(sizeof(Scatter) == sizeof(rtw_scatter), "rtw::Scatter mirrors rtw.h");
+// lib.rs:97-117 sample_ray's value for a caller's ray, laid out as rtw_sample
+struct Sample {
+  Color color;
+  uint32_t segments;
+  uint64_t stream;
+  uint32_t flags, reserved;
+  bool missed() const { return flags & RTW_SAMPLE_END_MISS; }
+  bool no_scatter() const { return flags & RTW_SAMPLE_END_NO_SCATTER; }
+  bool depth_exhausted() const { return flags & RTW_SAMPLE_END_DEPTH; }
+  bool bad() const { return flags & RTW_SAMPLE_BAD_RAY; }
+};
+static_assert(sizeof(Sample) == sizeof(rtw_sample), "rtw::Sample mirrors rtw.h");
 
 struct Camera {
   rtw_camera c{};
@@ -191,6 +204,15 @@ class World {
     const float bg[3] = {background.x, background.y, background.z};
     check(rtw_scatter_rays(s_, device, rays.size(), rays.data(), hits.data(), bg, rays.data(), sc.data(), st));
     return sc;
+  }
+  // Raytracer::sample_ray for every ray (lib.rs:97-117), each whole path on the GPU in one launch; a ray's stream
+  // word (non-zero) seeds its path's draws; blocking
+  std::vector<Sample> sample_rays(const std::vector<Ray>& rays, Color background, uint32_t max_depth = 50,
+                                  int device = -1, rtw_stats* st = nullptr) const {
+    std::vector<Sample> out(rays.size());
+    const float bg[3] = {background.x, background.y, background.z};
+    check(rtw_sample_rays(s_, device, rays.size(), rays.data(), bg, max_depth, out.data(), st));
+    return out;
   }
 
  private:

@@ -1,8 +1,9 @@
 // rtw_kernel.hip — what of the gfx950 path-tracing megakernel's host side needs the device compiler: the kernels
 // that are no templates (reduce_kernel, unpack_tiles_kernel, the libm and reciprocal diagnostics, with the two calls
 // that launch the latter), the tuning knobs, pick_kernel (which path-kernel variant a scene runs) and the launches
-// (enqueue_render, enqueue_hit_rays, enqueue_scatter_rays, enqueue_camera_rays, enqueue_unpack), which share one cache
-// of resident grids (resident_blocks), the walk's tuning (tune_walk) and the queries' launch (launch_query).  The
+// (enqueue_render, enqueue_hit_rays, enqueue_sample_rays, enqueue_scatter_rays, enqueue_camera_rays, enqueue_unpack),
+// which share one cache of resident grids (resident_blocks), the walk's tuning (tune_walk) and the one-record-per-lane
+// queries' launch (launch_query).  The
 // scene's device copies, statistics and the render entry points are plain HIP runtime code in rtw_render.cpp, the
 // ray-query entry points in rtw_query.cpp.  The device code is in headers that this unit and rtw_kernel_mesh.hip (the
 // F_MESHES variants, under their own compiler flags) both include.
@@ -36,6 +37,9 @@
 // its radiance to an ordered sample buffer that reduce_kernel sums per pixel in sample order.
 // Ray queries (rtw_hit_rays*): hit_kernel<K> (rtw_query_kernel.hpp) runs caller rays through the same trace_begin /
 // trace_run / hit_record under the scene's own K, one ray per lane, grid-stride; instantiated beside path_kernel<.., K>.
+// Radiance queries (rtw_sample_rays*): sample_kernel<K> (rtw_sample_kernel.hpp) is path_kernel's persistent loop over
+// caller rays -- index pool, ballot + mbcnt regeneration, resumable trace_run, the shading body -- without the camera,
+// the start ring and the sample buffer: one 32-byte record per ray.  Instantiated beside path_kernel<.., K> as well.
 // Scatter and camera-ray queries (rtw_scatter_rays*, rtw_camera_rays*): scatter_kernel and camera_rays_kernel
 // (rtw_shade_kernel.hpp) restate the materials and start_path over record arrays; one instantiation each, this unit only.
 // Variants: path_kernel<COUNT, KernelCfg K> -- one plain aggregate (stack rows, spill, waves / SIMD, feature set,
@@ -500,6 +504,55 @@ int enqueue_hit_rays(Scene& sc, DeviceCopy& c, uint64_t n, const void* d_rays, v
   a.spill = static_cast<int32_t*>(c.spill.p);
   a.err = c.err_host;
   return launch_query(var.hit, "hit_kernel launch", resident, k.blk, n, a, stream, ev0, ev1);
+}
+
+// Radiance queries (rtw_sample_rays*): the scene's variant and a render's whole launch tuning (tune_launch: quota16,
+// leaf16, regen_min, the batch, the spill split) on the sample kernel's own resident capacity; the batch shrinks for a
+// small launch by the render's rule (pass_batch; knob RTW_BATCH sets it outright).  The device copy's counters and
+// dispenser words are zeroed on the stream first, and the dispenser again before every further launch of a long array.
+int enqueue_sample_rays(Scene& sc, DeviceCopy& c, uint64_t n, const void* d_rays, const float* bg, uint32_t max_depth,
+                        void* d_samples, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+  const Knobs kn = read_knobs();
+  const Variant var = path_kernel_variant(sc.flat, kn);
+  const KernelCfg& k = var.cfg;
+  const int resident = resident_blocks(c, GRID_SAMPLE, (const void*)var.sample, k.blk, "sample kernel", kn.verbose);
+  RenderArgs r;
+  memset(&r, 0, sizeof r);
+  tune_launch(r, kn, sc.flat, k, resident);
+  if (int e = grow(c.spill, (size_t)r.spill_depth * r.spill_lanes * sizeof(int32_t))) return e;
+  SampleArgs a;
+  memset(&a, 0, sizeof a);
+  a.scene = c.scene;
+  a.max_depth = max_depth;
+  memcpy(a.bg, bg, sizeof a.bg);
+  a.time_lo = sc.flat.time_lo;
+  a.time_hi = sc.flat.time_hi;
+  a.quota16 = r.quota16;
+  a.leaf16 = r.leaf16;
+  a.regen_min = r.regen_min;
+  a.spill_lanes = r.spill_lanes;
+  a.spill = static_cast<int32_t*>(c.spill.p);
+  a.counters = c.counters;
+  a.queue = c.counters + 32;
+  a.err = c.err_host;
+  const uint64_t waves = (uint64_t)resident * (uint32_t)k.blk / 64u;
+  HIPCHK(hipMemsetAsync(c.counters, 0, COUNTER_WORDS * sizeof(unsigned long long), stream), "hipMemsetAsync");
+  if (ev0) HIPCHK(hipEventRecord(ev0, stream), "hipEventRecord");
+  for (uint64_t first = 0; first < n; first += SAMPLE_LAUNCH_MAX) {
+    const uint64_t m = std::min(SAMPLE_LAUNCH_MAX, n - first);
+    if (first) HIPCHK(hipMemsetAsync(a.queue, 0, DISP * DISP_STRIDE * sizeof(unsigned long long), stream),
+                      "hipMemsetAsync(queue)");
+    a.rays = static_cast<const char*>(d_rays) + first * sizeof(rtw_ray);
+    a.samples = static_cast<char*>(d_samples) + first * sizeof(rtw_sample);
+    a.n = (uint32_t)m;
+    a.batch = kn.batch.set ? r.batch : pass_batch(r.batch, m, waves);
+    // persistent: at most the resident capacity, and no more workgroups than the rays can occupy
+    const int grid = (int)std::min<uint64_t>((uint64_t)resident, (m + (uint32_t)k.blk - 1u) / (uint32_t)k.blk);
+    hipLaunchKernelGGL(var.sample, dim3(grid), dim3(k.blk), 0, stream, a);
+    HIPCHK(hipGetLastError(), "sample_kernel launch");
+  }
+  if (ev1) HIPCHK(hipEventRecord(ev1, stream), "hipEventRecord");
+  return RTW_OK;
 }
 
 // Scatter queries (rtw_scatter_rays*): the scene's tables, the per-material shading records and the record arrays.

@@ -1,9 +1,9 @@
-// rtw_query.cpp — the six ray-query entry points of one device (rtw_hit_rays, rtw_scatter_rays, rtw_camera_rays, each
-// in a host form over host arrays and a device form over device arrays on the caller's stream) and their argument
-// checks, on one shared runtime: Query opens the scene's device copy, stages the host forms' arrays chunk by chunk,
-// and waits for and reports the device forms' statistics.  Plain HIP runtime API: the kernels and their launches are
-// rtw_kernel.hip's (enqueue_hit_rays, enqueue_scatter_rays, enqueue_camera_rays); the device copies, need_copy, the
-// traversal guard's error word and the frame checks are rtw_render.cpp's.
+// rtw_query.cpp — the eight ray-query entry points of one device (rtw_hit_rays, rtw_sample_rays, rtw_scatter_rays,
+// rtw_camera_rays, each in a host form over host arrays and a device form over device arrays on the caller's stream)
+// and their argument checks, on one shared runtime: Query opens the scene's device copy, stages the host forms' arrays
+// chunk by chunk, and waits for and reports the device forms' statistics.  Plain HIP runtime API: the kernels and their
+// launches are rtw_kernel.hip's (enqueue_hit_rays, enqueue_sample_rays, enqueue_scatter_rays, enqueue_camera_rays); the
+// device copies, need_copy, the traversal guard's error word and the frame checks are rtw_render.cpp's.
 //
 // Every call checks in this order: a NULL argument (RTW_EINVAL), the scene's state (RTW_ESTATE; a flattened scene is
 // asked for, so that a commit that found no device answers RTW_ENODEV), for the camera calls the frame, the path range
@@ -20,15 +20,17 @@
 namespace rtw {
 namespace {
 
-// What differs between the queries beyond their arrays.  Only hit_kernel walks the BVH, so only its calls look at the
-// traversal guard's error word (before anything is enqueued and after every wait) and count rays.
+// What differs between the queries beyond their arrays.  Only hit_kernel and sample_kernel walk the BVH, so only their
+// calls look at the traversal guard's error word (before anything is enqueued and after every wait) and count rays: a
+// hit query's are its n records, a radiance query's the segments its kernel counted on the device, as a render's.
 struct Kind {
   const char* kernel;
-  bool guard;  // check_guard before enqueueing and after waiting
-  bool rays;   // stats->rays = n (else 0)
+  bool guard;    // check_guard before enqueueing and after waiting
+  bool rays;     // stats->rays = n (else 0)
+  bool counted;  // stats->rays = the device's segment counter (DeviceCopy::counters[0]), stats->paths = n
 };
-constexpr Kind HIT{"hit_kernel", true, true}, SCATTER{"scatter_kernel", false, false},
-    CAMERA{"camera_rays_kernel", false, false};
+constexpr Kind HIT{"hit_kernel", true, true, false}, SCATTER{"scatter_kernel", false, false, false},
+    CAMERA{"camera_rays_kernel", false, false, false}, SAMPLE{"sample_kernel", true, false, true};
 
 // One array of a host form: staged through `buf` in chunks, copied in from `in` and / or out to `out` (or NULL)
 struct Staged {
@@ -87,6 +89,7 @@ struct Query {
       st.kernel_ms += ms;
       if (kind.guard)
         if (int e = check_guard(*c)) return e;
+      if (int e = count_segments()) return e;
     }
     return report(n, stats);
   }
@@ -100,11 +103,22 @@ struct Query {
     if (kind.guard)
       if (int e = check_guard(*c)) return e;
     st.kernel_ms = ms;
+    if (int e = count_segments()) return e;
     return report(n, stats);
+  }
+
+  // after a wait: the segments the launches since enqueue_sample_rays' memset counted
+  int count_segments() {
+    if (!kind.counted) return RTW_OK;
+    unsigned long long segments = 0;
+    HIPCHK(hipMemcpy(&segments, c->counters, sizeof segments, hipMemcpyDeviceToHost), "hipMemcpy(counters)");
+    st.rays += segments;
+    return RTW_OK;
   }
 
   int report(uint64_t n, rtw_stats* stats) {
     if (kind.rays) st.rays = n;
+    if (kind.counted) st.paths = n;
     st.total_ms = ms_since(t0);
     if (stats) *stats = st;
     return RTW_OK;
@@ -181,6 +195,42 @@ int rtw_hit_rays_device(rtw_scene* s, int device, uint64_t n, const void* d_rays
   if (int e = q.open(s, device, stats != nullptr)) return e;
   const hipStream_t on = abi_stream(stream);
   if (int e = enqueue_hit_rays(s->s, *q.c, n, d_rays, d_hits, on, q.e0, q.e1)) return e;
+  return q.finish_device(on, n, stats);
+}
+
+int rtw_sample_rays(rtw_scene* s, int device, uint64_t n, const void* rays, const float background[3],
+                    uint32_t max_depth, void* samples, rtw_stats* stats) {
+  Query q(SAMPLE);
+  if (int e = check_scene(s, !background || (n && (!rays || !samples)))) return e;
+  if (n == 0) return no_records(stats);
+  const rtw_ray* r = static_cast<const rtw_ray*>(rays);
+  const float lo = s->s.flat.time_lo, hi = s->s.flat.time_hi;
+  for (uint64_t k = 0; k < n; ++k) {
+    if (!(r[k].time >= lo && r[k].time <= hi))
+      return fail(RTW_EINVAL, "ray %llu: time %g outside the committed motion range [%g, %g]", (unsigned long long)k,
+                  r[k].time, lo, hi);
+    if (r[k].stream == 0)
+      return fail(RTW_EINVAL, "ray %llu: stream word 0 (the generator never leaves that state)", (unsigned long long)k);
+  }
+  if (int e = q.open(s, device, true)) return e;
+  DeviceCopy& c = *q.c;
+  const auto enqueue = [&](uint64_t, uint64_t m) {
+    return enqueue_sample_rays(s->s, c, m, c.qrays.p, background, max_depth, c.qsamples.p, nullptr, q.e0, q.e1);
+  };
+  return q.run_staged(n, stats, {{c.qrays, rays, nullptr, sizeof(rtw_ray), "hipMemcpy(rays)"},
+                                 {c.qsamples, nullptr, samples, sizeof(rtw_sample), "hipMemcpy(samples)"}}, enqueue);
+}
+
+int rtw_sample_rays_device(rtw_scene* s, int device, uint64_t n, const void* d_rays, const float background[3],
+                           uint32_t max_depth, void* d_samples, void* stream, rtw_stats* stats) {
+  Query q(SAMPLE);
+  if (int e = check_scene(s, !background || (n && (!d_rays || !d_samples)))) return e;
+  if (n == 0) return no_records(stats);
+  if (((uintptr_t)d_rays | (uintptr_t)d_samples) & 15u)
+    return fail(RTW_EINVAL, "d_rays and d_samples must be 16-byte aligned");
+  if (int e = q.open(s, device, stats != nullptr)) return e;
+  const hipStream_t on = abi_stream(stream);
+  if (int e = enqueue_sample_rays(s->s, *q.c, n, d_rays, background, max_depth, d_samples, on, q.e0, q.e1)) return e;
   return q.finish_device(on, n, stats);
 }
 

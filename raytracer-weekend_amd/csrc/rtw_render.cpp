@@ -112,7 +112,7 @@ void release(Scene& s) {
     if (c.counters) hipFree(c.counters);
     if (c.err_host) hipHostFree(c.err_host);
     for (DevBuf* b : {&c.sbuf, &c.spill, &c.image, &c.tiles, &c.packed, &c.gathered, &c.gather_ids, &c.qrays, &c.qhits,
-                       &c.mshade, &c.qscatter})
+                       &c.mshade, &c.qscatter, &c.qsamples})
       free_buf(*b);
     for (hipEvent_t e : {c.ev[0], c.ev[1], c.gev[0], c.gev[1]})
       if (e) hipEventDestroy(e);

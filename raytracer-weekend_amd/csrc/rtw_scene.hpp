@@ -102,7 +102,7 @@ struct ResidentGrid {
   const void* fn = nullptr;
   int blocks = 0;
 };
-enum GridSlot { GRID_PATH, GRID_PATH_COUNT, GRID_HIT, GRID_SCATTER, GRID_CAMERA, GRID_SLOTS };
+enum GridSlot { GRID_PATH, GRID_PATH_COUNT, GRID_HIT, GRID_SCATTER, GRID_CAMERA, GRID_SAMPLE, GRID_SLOTS };
 
 struct DeviceCopy {
   int device = -1;  // the logical device the caller names (rtw_render_device, rtw_render_multi's device d)
@@ -118,13 +118,14 @@ struct DeviceCopy {
   DevBuf spill;                            // traversal-stack overflow (trees deeper than the LDS stack)
   hipEvent_t kev[64][2] = {};              // pairs around path-kernel launches (ring, rtw_path_kernel_times)
   uint32_t kev_head = 0, kev_count = 0;
-  ResidentGrid grids[GRID_SLOTS];          // the path kernel (plain, counting) and the three query kernels
+  ResidentGrid grids[GRID_SLOTS];          // the path kernel (plain, counting) and the four query kernels
   // device buffers kept across render calls (grown, never shrunk; freed by release()): a
   // 30-camera animation through rtw_render does no hipMalloc after the first frame
   DevBuf image, tiles, packed, gathered, gather_ids;
   DevBuf qrays, qhits;                     // rtw_hit_rays' staging: one chunk of rays and of records
   DevBuf mshade;                           // Flat::mshade (uploaded with the scene; scatter_kernel's material table)
   DevBuf qscatter;                         // rtw_scatter_rays' staging: one chunk of rtw_scatter records
+  DevBuf qsamples;                         // rtw_sample_rays' staging: one chunk of rtw_sample records
   hipEvent_t ev[2] = {nullptr, nullptr};   // pair timing rtw_render / multi calls (copy_events)
   hipStream_t stream = nullptr;            // rtw_render_multi's stream on this device
   hipEvent_t gev[2] = {nullptr, nullptr};  // pair around rtw_render_multi's gather (device 0)
@@ -246,6 +247,11 @@ int enqueue_scatter_rays(Scene& s, DeviceCopy& c, uint64_t n, const void* d_rays
 // the caller has checked the frame and the shutter (rtw_query.cpp camera_rays_check)
 int enqueue_camera_rays(DeviceCopy& c, const Frame& f, uint64_t first, uint64_t n, void* d_rays, hipStream_t stream,
                         hipEvent_t ev0, hipEvent_t ev1);
+// enqueue sample_ray for n rays (rtw_ray[n] -> rtw_sample[n], device arrays) on `stream` of c.device, which must be
+// current: the dispenser and the counters zeroed, then one persistent launch per 2^31 rays; ev0 / ev1 (or NULL) are
+// recorded around them.  Afterwards c.counters[0] holds the segments traced.
+int enqueue_sample_rays(Scene& s, DeviceCopy& c, uint64_t n, const void* d_rays, const float* bg, uint32_t max_depth,
+                        void* d_samples, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1);
 int enqueue_unpack(uint32_t w, uint32_t h, const uint32_t* d_tiles, uint32_t n_tiles, const float* d_packed,
                    float* d_image, hipStream_t stream);
 
