@@ -1,6 +1,7 @@
 // rtw_dev_shade.hpp — what shading needs of the winner: its hit record (Rec, hit_record: hittable/mod.rs:32-48), the
 // textures (checker, Perlin noise, image lookup, tex_value: texture.rs, image_texture.rs, perlin.rs) and Schlick's
-// reflectance.  The materials themselves are one body in path_kernel (rtw_path_kernel.hpp).
+// reflectance, and the materials (mat_kind, mat_attenuation, mat_direction): the one body that path_kernel,
+// sample_kernel and scatter_kernel all shade with.
 #pragma once
 #include "rtw_dev_hit.hpp"
 
@@ -273,6 +274,69 @@ __device__ __forceinline__ float reflectance(float cosine, float r0) {  // mater
   float x = 1.0f - cosine;
   float x2 = x * x;
   return r0 + (1.0f - r0) * (x * (x2 * x2));  // powi(5) as LLVM expands it
+}
+
+// ---- the materials (material.rs:42-165, light_source.rs:17-24): one body for every material, so a wave mixing
+// materials runs the rejection loop, unit() and the texture lookup once instead of once per material branch.  Each
+// material's draws and f32 operations are the reference's.  In three pieces, between which a kernel draws
+// rs = rand_in_unit_sphere (for lam, met and iso) and takes ud = unit(lam ? rs : d_in) itself; the throughput, the
+// terminal rules and the output are each kernel's own (path_kernel, sample_kernel, scatter_kernel).
+struct MatKind {
+  uint32_t mode;  // DevShade's SM_*
+  bool light, lam, met, iso;  // none of them: a Dielectric
+};
+template <uint32_t FEAT>
+__device__ __forceinline__ MatKind mat_kind(uint32_t kind) {
+  const uint32_t mt = kind & 0xffu;
+  MatKind k;
+  k.mode = (kind >> 8) & 0xfu;
+  k.light = (FEAT & F_LIGHT) && mt == MT_LIGHT;
+  k.lam = (FEAT & F_LAMBERT) && mt == MT_LAMBERT;
+  k.met = (FEAT & F_METAL) && mt == MT_METAL;
+  k.iso = (FEAT & F_ISO) && mt == MT_ISOTROPIC;
+  return k;
+}
+// Scatter::attenuation, or a light's emission.  even(): the checker's even colour (DevShade::b), a callable so that a
+// kernel short of registers can read it here, where it is used
+template <uint32_t FEAT, class Even>
+__device__ __forceinline__ V3 mat_attenuation(const DevScene& S, const DevShade& sh, const MatKind& k, const Rec& h,
+                                              Even even) {
+  V3 att = mk(1.f, 1.f, 1.f);  // Dielectric: attenuation (1,1,1)
+  if (k.met) {
+    att = ld3(sh.a);
+  } else if (k.light || k.lam || k.iso) {
+    if (k.mode == SM_SOLID) att = ld3(sh.a);  // SolidColor::value
+    else if ((FEAT & F_CHECKER) && k.mode == SM_CHECKER)
+      att = checker_odd(sh.param * h.p.x, sh.param * h.p.y, sh.param * h.p.z) ? ld3(sh.a) : even();
+    else if ((FEAT & F_IMAGE) && k.mode == SM_IMAGE)  // (the monument's texture: no record chain)
+      att = image_texel(S, __float_as_uint(sh.a[0]), __float_as_uint(sh.a[1]), __float_as_uint(sh.a[2]), h.u, h.v);
+    else if (FEAT & F_TEXGEN) att = tex_value<FEAT>(S, S.mats[h.mat].tex, h.u, h.v, h.p);
+  }
+  return att;
+}
+// The scattered direction of a material that is no light; absorbed: a Metal ray below the surface (emitted() is black)
+template <uint32_t FEAT>
+__device__ __forceinline__ V3 mat_direction(const DevShade& sh, const MatKind& k, const Rec& h, V3 ud, V3 rs,
+                                            uint64_t& rng, bool& absorbed) {
+  V3 dir = rs;  // Isotropic (material.rs:155-165): never absorbs
+  if (k.lam) {  // material.rs:42-56
+    dir = add(h.n, ud);
+    if (near_zero(dir)) dir = h.n;
+  } else if (k.met) {  // material.rs:78-95
+    dir = add(reflect(ud, h.n), scale(rs, sh.param));
+    absorbed = !(dot(dir, h.n) > 0.0f);
+  } else if (!k.iso && (FEAT & F_DIEL)) {  // Dielectric, material.rs:116-142
+    // 1 / ir (material.rs:120) and Schlick's r0 (:108-112) for both ratios: the same f32
+    // operations, evaluated once by the flattener (DevShade::a)
+    const float ratio = h.front ? sh.a[0] : sh.param;
+    const float r0 = h.front ? sh.a[1] : sh.a[2];
+    const float cos_t = fminf(dot(neg(ud), h.n), 1.0f);
+    const float sin_t = sqrtf(1.0f - cos_t * cos_t);
+    const bool cannot = (ratio * sin_t) > 1.0f;
+    if (cannot || reflectance(cos_t, r0) > gen_f32(rng)) dir = reflect(ud, h.n);
+    else dir = refract(ud, h.n, ratio);
+  }
+  return dir;
 }
 
 }  // namespace dev

@@ -17,7 +17,7 @@
 //   [Box<dyn Hittable>]::hit (hittable/mod.rs:57-69)    -> 4-wide BVH walk (or the flat list), min t,
 //                                                        ties -> the larger DFS key (rtw_dev_trace.hpp over
 //                                                        rtw_dev_hit.hpp's primitive tests)
-//   Material::scatter / emitted (material.rs, light_source.rs) -> path_kernel's shading body; Texture::value
+//   Material::scatter / emitted (material.rs, light_source.rs) -> the materials' one body, Texture::value
 //   (texture.rs, image_texture.rs) and the hit record -> rtw_dev_shade.hpp; Camera::get_ray (camera.rs:66-74) ->
 //   start_path (rtw_path_kernel.hpp); the f32 arithmetic and the RNG under all of them -> rtw_dev_math.hpp
 //
@@ -41,7 +41,8 @@
 // caller rays -- index pool, ballot + mbcnt regeneration, resumable trace_run, the shading body -- without the camera,
 // the start ring and the sample buffer: one 32-byte record per ray.  Instantiated beside path_kernel<.., K> as well.
 // Scatter and camera-ray queries (rtw_scatter_rays*, rtw_camera_rays*): scatter_kernel and camera_rays_kernel
-// (rtw_shade_kernel.hpp) restate the materials and start_path over record arrays; one instantiation each, this unit only.
+// (rtw_shade_kernel.hpp) run the materials' body and restate start_path over record arrays; one instantiation each, this
+// unit only.
 // Variants: path_kernel<COUNT, KernelCfg K> -- one plain aggregate (stack rows, spill, waves / SIMD, feature set,
 // workgroup size, LDS node table, half nodes, 16-bit stack) is the template argument, defines every property derived
 // from it, and travels with the kernel to the host (Variant, rtw_variants.hpp), which sizes the launch from it.
@@ -311,6 +312,10 @@ static int launch_query(Kernel kernel, const char* what, int resident, int block
 // consecutive ids: path_kernel's start ring (SRING) builds 64 starts from pool_next + lane without a bound check.
 static uint32_t batch_ids(int v) { return (uint32_t)std::min(65536, std::max(64, v)) & ~63u; }
 
+// The DISP path-id dispensers (path_kernel; sample_kernel uses the first), DISP_STRIDE words apart, behind the
+// counters' 32 statistics words
+static unsigned long long* dispensers(const DeviceCopy& c) { return c.counters + 32; }
+
 // enqueue_render, part 1: the RenderArgs of a frame and its tiles, all but the launch tuning.  Pure host arithmetic.
 static RenderArgs frame_args(const DeviceCopy& c, const Frame& f, const TileSet& ts, float* d_out) {
   const rtw_camera* cam = f.cam;
@@ -351,7 +356,7 @@ static RenderArgs frame_args(const DeviceCopy& c, const Frame& f, const TileSet&
   a.seed_hash = z ^ (z >> 31);
   a.out = d_out;
   a.counters = c.counters;
-  a.queue = c.counters + 32;  // the DISP path-id dispensers (path_kernel), DISP_STRIDE words apart
+  a.queue = dispensers(c);
   return a;
 }
 
@@ -375,15 +380,18 @@ static WalkTuning tune_walk(const Knobs& kn, const Flat& flat, const KernelCfg& 
   return t;
 }
 
-// enqueue_render, part 2: the launch tuning of variant k on `grid` resident workgroups, into a.  a.batch is the
-// full-frame value: pass_batch shrinks it for a small pass.
-static void tune_launch(RenderArgs& a, const Knobs& kn, const Flat& flat, const KernelCfg& k, int grid) {
+// The launch tuning of variant k's persistent loop on `grid` resident workgroups: what a render's path kernel
+// (enqueue_render, part 2) and a radiance query's sample kernel share.  batch is the full-frame value: pass_batch
+// shrinks it for a small pass.
+struct LaunchTuning {
+  WalkTuning walk;
+  uint32_t quota16, regen_min, batch;
+};
+static LaunchTuning tune_launch(const Knobs& kn, const Flat& flat, const KernelCfg& k, int grid) {
+  LaunchTuning a;
+  a.walk = tune_walk(kn, flat, k, grid);
   // see trace_run (measured best of 4..16 on jumpy-balls); tuning knob RTW_QUOTA16 (1..16)
   a.quota16 = (uint32_t)std::min(16, std::max(1, kn.quota16.get(12)));
-  const WalkTuning t = tune_walk(kn, flat, k, grid);
-  a.leaf16 = t.leaf16;
-  a.spill_depth = t.spill_depth;
-  a.spill_lanes = t.spill_lanes;
   // whole wave-loads of ids only (batch_ids): the start ring makes 64 path starts from 64 consecutive ids of a batch.
   // The 1024-lane LDS-node kernel and the BVH-less list kernels: 1024 ids per atomic (a shorter end-of-frame
   // tail; jumpy-1080p +1.2%, cornell-800 +0.5% over 2048, profiles/r03/experiments k3 / k4); the mesh
@@ -402,6 +410,7 @@ static void tune_launch(RenderArgs& a, const Knobs& kn, const Flat& flat, const 
   const bool boxed = (flat.features & ~F_SMOKE) == 0;
   const int regen_dflt = k.ldsn_ring() ? REGEN_RING_LDSN : (k.sring() ? REGEN_RING : (boxed ? 8 : 24));
   a.regen_min = (uint32_t)std::min(64, std::max(1, kn.regen_min.get(regen_dflt)));
+  return a;
 }
 
 // Small frames: fewer ids per atomic, halving until every resident wave can take >= 32 batches.  configs[0]
@@ -433,17 +442,21 @@ static int run_passes(Scene& sc, DeviceCopy& c, RenderArgs& a, const Knobs& kn, 
   const KernelCfg& k = var.cfg;
   const int grid = resident_blocks(c, count ? GRID_PATH_COUNT : GRID_PATH, (const void*)var.fn[count], k.blk,
                                    "path kernel", kn.verbose);
-  tune_launch(a, kn, sc.flat, k, grid);
+  const LaunchTuning t = tune_launch(kn, sc.flat, k, grid);
+  a.quota16 = t.quota16;
+  a.leaf16 = t.walk.leaf16;
+  a.regen_min = t.regen_min;
+  a.spill_depth = t.walk.spill_depth;
+  a.spill_lanes = t.walk.spill_lanes;
   // (first render of a deep tree only)
   if (int e = grow(c.spill, (size_t)a.spill_depth * a.spill_lanes * sizeof(int32_t))) return e;
   a.spill = static_cast<int32_t*>(c.spill.p);
-  const uint32_t batch0 = a.batch;
   const uint64_t waves = (uint64_t)grid * (uint32_t)k.blk / 64u;
   for (uint32_t base = 0; base < n_slots; base += slots_per_pass) {
     const uint32_t ns = std::min(slots_per_pass, n_slots - base);
     a.slot_base = base;
     a.n_paths = (uint64_t)ns * per_slot;
-    a.batch = kn.batch.set ? batch0 : pass_batch(batch0, a.n_paths, waves);
+    a.batch = kn.batch.set ? t.batch : pass_batch(t.batch, a.n_paths, waves);
     if (base) HIPCHK(hipMemsetAsync(a.queue, 0, DISP * DISP_STRIDE * sizeof(unsigned long long), stream),
                      "hipMemsetAsync(queue)");
     hipEvent_t* ke = c.kev[c.kev_head];
@@ -516,10 +529,8 @@ int enqueue_sample_rays(Scene& sc, DeviceCopy& c, uint64_t n, const void* d_rays
   const Variant var = path_kernel_variant(sc.flat, kn);
   const KernelCfg& k = var.cfg;
   const int resident = resident_blocks(c, GRID_SAMPLE, (const void*)var.sample, k.blk, "sample kernel", kn.verbose);
-  RenderArgs r;
-  memset(&r, 0, sizeof r);
-  tune_launch(r, kn, sc.flat, k, resident);
-  if (int e = grow(c.spill, (size_t)r.spill_depth * r.spill_lanes * sizeof(int32_t))) return e;
+  const LaunchTuning t = tune_launch(kn, sc.flat, k, resident);
+  if (int e = grow(c.spill, (size_t)t.walk.spill_depth * t.walk.spill_lanes * sizeof(int32_t))) return e;
   SampleArgs a;
   memset(&a, 0, sizeof a);
   a.scene = c.scene;
@@ -527,13 +538,13 @@ int enqueue_sample_rays(Scene& sc, DeviceCopy& c, uint64_t n, const void* d_rays
   memcpy(a.bg, bg, sizeof a.bg);
   a.time_lo = sc.flat.time_lo;
   a.time_hi = sc.flat.time_hi;
-  a.quota16 = r.quota16;
-  a.leaf16 = r.leaf16;
-  a.regen_min = r.regen_min;
-  a.spill_lanes = r.spill_lanes;
+  a.quota16 = t.quota16;
+  a.leaf16 = t.walk.leaf16;
+  a.regen_min = t.regen_min;
+  a.spill_lanes = t.walk.spill_lanes;
   a.spill = static_cast<int32_t*>(c.spill.p);
   a.counters = c.counters;
-  a.queue = c.counters + 32;
+  a.queue = dispensers(c);
   a.err = c.err_host;
   const uint64_t waves = (uint64_t)resident * (uint32_t)k.blk / 64u;
   HIPCHK(hipMemsetAsync(c.counters, 0, COUNTER_WORDS * sizeof(unsigned long long), stream), "hipMemsetAsync");
@@ -545,7 +556,7 @@ int enqueue_sample_rays(Scene& sc, DeviceCopy& c, uint64_t n, const void* d_rays
     a.rays = static_cast<const char*>(d_rays) + first * sizeof(rtw_ray);
     a.samples = static_cast<char*>(d_samples) + first * sizeof(rtw_sample);
     a.n = (uint32_t)m;
-    a.batch = kn.batch.set ? r.batch : pass_batch(r.batch, m, waves);
+    a.batch = kn.batch.set ? t.batch : pass_batch(t.batch, m, waves);
     // persistent: at most the resident capacity, and no more workgroups than the rays can occupy
     const int grid = (int)std::min<uint64_t>((uint64_t)resident, (m + (uint32_t)k.blk - 1u) / (uint32_t)k.blk);
     hipLaunchKernelGGL(var.sample, dim3(grid), dim3(k.blk), 0, stream, a);

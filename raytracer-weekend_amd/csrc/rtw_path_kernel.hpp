@@ -193,27 +193,38 @@ struct KernelCfg {
   constexpr uint32_t node_quads() const { return half ? 7u : 8u; }  // 16-B quads per node (DevNode4h / DevNode4)
   constexpr bool codes16_stack() const { return ncap > 0 || s16; }  // the LDS stack holds 16-bit entries (stk16)
   constexpr int far_lds_nodes() const { return half ? 0 : ncap; }   // trace_far reads f32 nodes: from LDS if there
+  // The walk's LDS arrays, in elements (1: unused).  The 32-bit stack columns, + 1: trace_run's branch-free push
+  constexpr int stk_words() const { return codes16_stack() ? 1 : (stack + 1) * blk; }
+  // the 16-bit stack columns: LDS-node variants STACK rows (window included); S16 (global nodes) STACK + 1 rows and
+  // `more` rows after them (path_kernel's LST rows)
+  constexpr int stk16_words(int more = 0) const { return ncap > 0 ? stack * blk : (s16 ? (stack + 1 + more) * blk : 1); }
+  // the node table (the S16 half-node mesh walk: the tree's top only, trace_run ROOT)
+  constexpr uint32_t lds_node_quads() const {
+    return ncap > 0 ? ncap * node_quads() : (root_lds() ? RTW_MESH_ROOT * node_quads() : 1u);
+  }
 };
+
+// The workgroup's copy of the node table into nodes_lds (K.lds_node_quads() quads), before the kernel's first
+// __syncthreads(): the whole table (K.ncap > 0) or the tree's top (K.root_lds())
+template <KernelCfg K>
+__device__ __forceinline__ void fill_nodes_lds(const DevScene& S, float4* nodes_lds) {
+  if constexpr (K.ncap > 0) {  // the host launches this variant only when Flat::codes16 and n_nodes <= NCAP
+    const float4* g = K.half ? reinterpret_cast<const float4*>(S.hnodes) : reinterpret_cast<const float4*>(S.nodes);
+    for (uint32_t k = threadIdx.x; k < S.n_nodes * K.node_quads(); k += K.blk) nodes_lds[k] = g[k];
+  }
+  if constexpr (K.root_lds()) {
+    const uint32_t nq = min(S.n_nodes, (uint32_t)RTW_MESH_ROOT) * K.node_quads();
+    if (threadIdx.x < nq) nodes_lds[threadIdx.x] = reinterpret_cast<const float4*>(S.hnodes)[threadIdx.x];
+  }
+}
 
 template <bool COUNT, KernelCfg K>
 __global__ __launch_bounds__(K.blk) __attribute__((amdgpu_waves_per_eu(K.occ, 8))) void path_kernel(RenderArgs a) {
-  // + 1: trace_run's branch-free push.  LDS-node variants use 16-bit entries, STACK rows (window included);
-  // S16 (global nodes, 16-bit entries): STACK + 1 rows of 16 bits
-  __shared__ int32_t stk_all[K.codes16_stack() ? 1 : (K.stack + 1) * K.blk];
+  __shared__ int32_t stk_all[K.stk_words()];
   // LST (the S16 mesh walk): 10 more 16-bit rows after its STACK + 1 hold the path state (below)
-  __shared__ uint16_t stk16_all[K.ncap > 0 ? K.stack * K.blk : (K.s16 ? (K.stack + 1 + K.lst_rows()) * K.blk : 1)];
-  // (the S16 half-node mesh walk: the root node only, trace_run ROOT)
-  __shared__ float4 nodes_lds[K.ncap > 0 ? K.ncap * K.node_quads()
-                                         : (K.root_lds() ? RTW_MESH_ROOT * K.node_quads() : 1)];
-  if constexpr (K.ncap > 0) {  // the host launches this variant only when Flat::codes16 and n_nodes <= NCAP
-    const float4* g = K.half ? reinterpret_cast<const float4*>(a.scene.hnodes)
-                             : reinterpret_cast<const float4*>(a.scene.nodes);
-    for (uint32_t k = threadIdx.x; k < a.scene.n_nodes * K.node_quads(); k += K.blk) nodes_lds[k] = g[k];
-  }
-  if constexpr (K.root_lds()) {
-    const uint32_t nq = min(a.scene.n_nodes, (uint32_t)RTW_MESH_ROOT) * K.node_quads();
-    if (threadIdx.x < nq) nodes_lds[threadIdx.x] = reinterpret_cast<const float4*>(a.scene.hnodes)[threadIdx.x];
-  }
+  __shared__ uint16_t stk16_all[K.stk16_words(K.lst_rows())];
+  __shared__ float4 nodes_lds[K.lds_node_quads()];
+  fill_nodes_lds<K>(a.scene, nodes_lds);
   // start_path's operands from LDS in the sphere and list-mode variants (their SGPR spills, and every
   // reload a v_readlane: cornell-800 +6%, jumpy +0.8%) and in the 6 / 7-wave mesh walk (S16): at 80 VGPRs its
   // SGPRs overflowed into VGPR lanes and 28 B per lane of scratch; with the LDS copy 12 B: monument-4k +4.5%,
@@ -560,57 +571,24 @@ __global__ __launch_bounds__(K.blk) __attribute__((amdgpu_waves_per_eu(K.occ, 8)
 #ifdef RTW_SHADE_DIAG  // COUNT-build diagnostic: shading sub-phases (hit record, unit + texture, scatter) in ph[7..9]
       phase(7);
 #endif
-      // One body for every material (material.rs:42-165, light_source.rs:17-24): a wave mixing
-      // materials runs the rejection loop, unit() and the texture lookup once instead of once per
-      // material branch.  Each material's draws and f32 operations are unchanged.
-      const uint32_t mt = sh.kind & 0xffu, mode = (sh.kind >> 8) & 0xfu;
-      const bool light = (K.feat & F_LIGHT) && mt == MT_LIGHT;
-      const bool lam = (K.feat & F_LAMBERT) && mt == MT_LAMBERT;
-      const bool met = (K.feat & F_METAL) && mt == MT_METAL;
-      const bool iso = (K.feat & F_ISO) && mt == MT_ISOTROPIC;
+      // the materials' one body (rtw_dev_shade.hpp), the rejection draw and unit() between its pieces
+      const MatKind kind = mat_kind<K.feat>(sh.kind);
       V3 rs = mk(0.f, 0.f, 0.f);
       phase(2);
-      if (lam || met || iso) rs = rand_in_unit_sphere<K.alignbit_draws()>(st.rng);  // vec3.rs:101-108
+      if (kind.lam || kind.met || kind.iso) rs = rand_in_unit_sphere<K.alignbit_draws()>(st.rng);  // vec3.rs:101-108
       phase(3);
-      const V3 ud = unit(lam ? rs : st.ray.d);                  // Lambertian: unit(rs); else unit(d_in)
-      V3 att = mk(1.f, 1.f, 1.f);                                 // Dielectric: attenuation (1,1,1)
-      if (met) {
-        att = ld3(sh.a);
-      } else if (light || lam || iso) {
-        if (mode == SM_SOLID) att = ld3(sh.a);  // SolidColor::value
-        else if ((K.feat & F_CHECKER) && mode == SM_CHECKER)
-          att = checker_odd(sh.param * h.p.x, sh.param * h.p.y, sh.param * h.p.z) ? ld3(sh.a)
-                                                                                   : ld3(LST ? S.shade[b.prim].b : sh.b);
-        else if ((K.feat & F_IMAGE) && mode == SM_IMAGE)  // (the monument's texture: no record chain)
-          att = image_texel(S, __float_as_uint(sh.a[0]), __float_as_uint(sh.a[1]), __float_as_uint(sh.a[2]), h.u, h.v);
-        else if (K.feat & F_TEXGEN) att = tex_value<K.feat>(S, S.mats[h.mat].tex, h.u, h.v, h.p);
-      }
+      const V3 ud = unit(kind.lam ? rs : st.ray.d);  // Lambertian: unit(rs); else unit(d_in)
+      // (LST: the checker's even colour from the table, see above)
+      const V3 att = mat_attenuation<K.feat>(S, sh, kind, h, [&] { return ld3(LST ? S.shade[b.prim].b : sh.b); });
 #ifdef RTW_SHADE_DIAG
       phase(8);
 #endif
       V3 Tn = mk(0.f, 0.f, 0.f);  // the throughput after this segment (scattering materials)
-      if (light) {  // emit, no scatter
+      if (kind.light) {  // emit, no scatter
         L = mul(path_T(), att);
         done = true;
       } else {
-        V3 dir = rs;  // Isotropic (material.rs:155-165): never absorbs
-        if (lam) {    // material.rs:42-56
-          dir = add(h.n, ud);
-          if (near_zero(dir)) dir = h.n;
-        } else if (met) {  // material.rs:78-95
-          dir = add(reflect(ud, h.n), scale(rs, sh.param));
-          done = !(dot(dir, h.n) > 0.0f);  // absorbed: emitted() is black
-        } else if (!iso && (K.feat & F_DIEL)) {  // Dielectric, material.rs:116-142
-          // 1 / ir (material.rs:120) and Schlick's r0 (:108-112) for both ratios: the same f32
-          // operations, evaluated once by the flattener (DevShade::a)
-          const float ratio = h.front ? sh.a[0] : sh.param;
-          const float r0 = h.front ? sh.a[1] : sh.a[2];
-          const float cos_t = fminf(dot(neg(ud), h.n), 1.0f);
-          const float sin_t = sqrtf(1.0f - cos_t * cos_t);
-          const bool cannot = (ratio * sin_t) > 1.0f;
-          if (cannot || reflectance(cos_t, r0) > gen_f32(st.rng)) dir = reflect(ud, h.n);
-          else dir = refract(ud, h.n, ratio);
-        }
+        const V3 dir = mat_direction<K.feat>(sh, kind, h, ud, rs, st.rng, done);  // done: absorbed
         const V3 Tp = path_T();
         const V3 T2 = mul(Tp, att);  // x * 1.0f == x: the Dielectric's T is unchanged
         // an absorbed Metal ray returns emitted() = black (material.rs:87, lib.rs:109-110), which the recursion's

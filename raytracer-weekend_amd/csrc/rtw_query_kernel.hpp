@@ -34,6 +34,36 @@ static_assert(sizeof(rtw_ray) == 40 && sizeof(rtw_hit) == 48, "rtw_ray / rtw_hit
 // a ray record starts on an 8-byte boundary (40 B each): its two 16-byte quads and the stream word
 typedef float ray_quad __attribute__((ext_vector_type(4), aligned(8)));
 typedef uint32_t ray_pair __attribute__((ext_vector_type(2), aligned(8)));
+// the record as it lies in memory (returned by value: with the quads as reference parameters sample_kernel's list and
+// mesh variants came out as other code, one with scratch; scripts/isa_diff.sh)
+struct RayRec {
+  ray_quad q0, q1;  // origin, direction.x | direction.y, .z, time, reserved
+  ray_pair q2;      // stream
+};
+__device__ __forceinline__ RayRec load_ray(const void* rays, uint64_t i) {
+  const char* rp = reinterpret_cast<const char*>(rays) + i * sizeof(rtw_ray);
+  RayRec r;
+  r.q0 = *reinterpret_cast<const ray_quad*>(rp);
+  r.q1 = *reinterpret_cast<const ray_quad*>(rp + 16);
+  r.q2 = *reinterpret_cast<const ray_pair*>(rp + 32);
+  return r;
+}
+__device__ __forceinline__ void store_ray(void* rays, uint64_t i, const RayRec& r) {
+  char* rp = reinterpret_cast<char*>(rays) + i * sizeof(rtw_ray);
+  *reinterpret_cast<ray_quad*>(rp) = r.q0;
+  *reinterpret_cast<ray_quad*>(rp + 16) = r.q1;
+  *reinterpret_cast<ray_pair*>(rp + 32) = r.q2;
+}
+// the record as the walk takes it: the Ray, and the stream word returned
+__device__ __forceinline__ uint64_t ray_of(const RayRec& r, Ray& ray) {
+  ray.o = mk(r.q0.x, r.q0.y, r.q0.z);
+  ray.d = mk(r.q0.w, r.q1.x, r.q1.y);
+  ray.time = r.q1.z;
+  return ((uint64_t)r.q2.y << 32) | r.q2.x;
+}
+__device__ __forceinline__ uint64_t load_ray(const void* rays, uint64_t i, Ray& ray) {
+  return ray_of(load_ray(rays, i), ray);
+}
 
 // Each lane owns one ray and a wave takes 64 consecutive ones (the caller's order decides coherence); grid-stride
 // over n, the grid at most the resident capacity, so an LDS-node workgroup copies its node table once.  The last
@@ -41,19 +71,10 @@ typedef uint32_t ray_pair __attribute__((ext_vector_type(2), aligned(8)));
 template <KernelCfg K>
 __global__ __launch_bounds__(K.blk) __attribute__((amdgpu_waves_per_eu(K.occ, 8))) void hit_kernel(QueryArgs a) {
   // path_kernel's LDS without the LST rows: the stack columns (+ 1: trace_run's branch-free push) and the node table
-  __shared__ int32_t stk_all[K.codes16_stack() ? 1 : (K.stack + 1) * K.blk];
-  __shared__ uint16_t stk16_all[K.ncap > 0 ? K.stack * K.blk : (K.s16 ? (K.stack + 1) * K.blk : 1)];
-  __shared__ float4 nodes_lds[K.ncap > 0 ? K.ncap * K.node_quads()
-                                         : (K.root_lds() ? RTW_MESH_ROOT * K.node_quads() : 1)];
-  if constexpr (K.ncap > 0) {  // the host launches this variant only when Flat::codes16 and n_nodes <= NCAP
-    const float4* g = K.half ? reinterpret_cast<const float4*>(a.scene.hnodes)
-                             : reinterpret_cast<const float4*>(a.scene.nodes);
-    for (uint32_t k = threadIdx.x; k < a.scene.n_nodes * K.node_quads(); k += K.blk) nodes_lds[k] = g[k];
-  }
-  if constexpr (K.root_lds()) {
-    const uint32_t nq = min(a.scene.n_nodes, (uint32_t)RTW_MESH_ROOT) * K.node_quads();
-    if (threadIdx.x < nq) nodes_lds[threadIdx.x] = reinterpret_cast<const float4*>(a.scene.hnodes)[threadIdx.x];
-  }
+  __shared__ int32_t stk_all[K.stk_words()];
+  __shared__ uint16_t stk16_all[K.stk16_words()];
+  __shared__ float4 nodes_lds[K.lds_node_quads()];
+  fill_nodes_lds<K>(a.scene, nodes_lds);
   __syncthreads();
   uint16_t* stk16 = stk16_all + threadIdx.x;
   int32_t* stk = stk_all + threadIdx.x;
@@ -67,15 +88,8 @@ __global__ __launch_bounds__(K.blk) __attribute__((amdgpu_waves_per_eu(K.occ, 8)
     const uint64_t i = base + (threadIdx.x & 63u);
     bool tripped = false;
     if (i < a.n) {
-      const char* rp = reinterpret_cast<const char*>(a.rays) + i * sizeof(rtw_ray);
-      const ray_quad r0 = *reinterpret_cast<const ray_quad*>(rp);       // origin, direction.x
-      const ray_quad r1 = *reinterpret_cast<const ray_quad*>(rp + 16);  // direction.y, .z, time, reserved
-      const ray_pair r2 = *reinterpret_cast<const ray_pair*>(rp + 32);  // stream
       Ray ray;
-      ray.o = mk(r0.x, r0.y, r0.z);
-      ray.d = mk(r0.w, r1.x, r1.y);
-      ray.time = r1.z;
-      const uint64_t seg = ((uint64_t)r2.y << 32) | r2.x;
+      const uint64_t seg = load_ray(a.rays, i, ray);
       // the BVH's moving-sphere boxes bound [time_lo, time_hi] only: a NaN time fails both compares
       const bool bad = !(ray.time >= a.time_lo && ray.time <= a.time_hi);
       float4 o0 = make_float4(0.f, 0.f, 0.f, 0.f), o1 = make_float4(0.f, 0.f, INFINITY, 0.f);

@@ -9,9 +9,10 @@
 // resumed across iterations under the render's quota16 / leaf16.  A regenerating lane loads its ray (two quads and the
 // stream pair) where path_kernel runs start_path; a ray that is not traced (a bad time, a zero stream word, or
 // max_depth = 0) is finished there, path_kernel's off-image case, and the wave draws again.  Each segment is
-// trace_begin / trace_run, hit_record<K.feat> with the per-primitive shading record, and path_kernel's shading body
-// restated with its L = T * terminal rules (T * 0, the solid_light shortcut): the same helpers, f32 operations and draw
-// order, so a record's colour is the render's sample bit for bit (tests/test_gpu_sample_rays.py).
+// trace_begin / trace_run, hit_record<K.feat> with the per-primitive shading record, and the materials' one body
+// (rtw_dev_shade.hpp: mat_kind, mat_attenuation, mat_direction) that path_kernel calls too, under path_kernel's
+// L = T * terminal rules (T * 0, the solid_light shortcut) written out here: the same f32 operations and draw order, so
+// a record's colour is the render's sample bit for bit (tests/test_gpu_sample_rays.py).
 //
 // What it leaves out of path_kernel: StartArgs and the start ring, the LST rows (the path state stays in VGPRs), SHARD
 // (one dispenser word), COUNT builds, the sample buffer and reduce_kernel: a finished path writes its 32-byte record at
@@ -52,19 +53,10 @@ template <KernelCfg K>
 __global__ __launch_bounds__(K.blk) __attribute__((amdgpu_waves_per_eu(K.occ, 8))) void sample_kernel(SampleArgs a) {
   // path_kernel's LDS without the LST rows, StartArgs and the ring: the stack columns (+ 1: trace_run's branch-free
   // push), the node table and the waves' index pools
-  __shared__ int32_t stk_all[K.codes16_stack() ? 1 : (K.stack + 1) * K.blk];
-  __shared__ uint16_t stk16_all[K.ncap > 0 ? K.stack * K.blk : (K.s16 ? (K.stack + 1) * K.blk : 1)];
-  __shared__ float4 nodes_lds[K.ncap > 0 ? K.ncap * K.node_quads()
-                                         : (K.root_lds() ? RTW_MESH_ROOT * K.node_quads() : 1)];
-  if constexpr (K.ncap > 0) {  // the host launches this variant only when Flat::codes16 and n_nodes <= NCAP
-    const float4* g = K.half ? reinterpret_cast<const float4*>(a.scene.hnodes)
-                             : reinterpret_cast<const float4*>(a.scene.nodes);
-    for (uint32_t k = threadIdx.x; k < a.scene.n_nodes * K.node_quads(); k += K.blk) nodes_lds[k] = g[k];
-  }
-  if constexpr (K.root_lds()) {
-    const uint32_t nq = min(a.scene.n_nodes, (uint32_t)RTW_MESH_ROOT) * K.node_quads();
-    if (threadIdx.x < nq) nodes_lds[threadIdx.x] = reinterpret_cast<const float4*>(a.scene.hnodes)[threadIdx.x];
-  }
+  __shared__ int32_t stk_all[K.stk_words()];
+  __shared__ uint16_t stk16_all[K.stk16_words()];
+  __shared__ float4 nodes_lds[K.lds_node_quads()];
+  fill_nodes_lds<K>(a.scene, nodes_lds);
   // the wave's index pool [next, end) and the batch lane 0 took (path_kernel's pool_lds)
   __shared__ uint64_t pool_lds[K.blk / 64][3];
   uint64_t* const pool = pool_lds[threadIdx.x >> 6];
@@ -120,14 +112,7 @@ __global__ __launch_bounds__(K.blk) __attribute__((amdgpu_waves_per_eu(K.occ, 8)
       if (!has) {
         const uint64_t id = rank < avail ? pool_next + rank : nb + (rank - avail);
         if (rank < avail || id < ne) {
-          const char* rp = reinterpret_cast<const char*>(a.rays) + id * sizeof(rtw_ray);
-          const ray_quad r0 = *reinterpret_cast<const ray_quad*>(rp);       // origin, direction.x
-          const ray_quad r1 = *reinterpret_cast<const ray_quad*>(rp + 16);  // direction.y, .z, time, reserved
-          const ray_pair r2 = *reinterpret_cast<const ray_pair*>(rp + 32);  // stream
-          const uint64_t word = ((uint64_t)r2.y << 32) | r2.x;
-          st.ray.o = mk(r0.x, r0.y, r0.z);
-          st.ray.d = mk(r0.w, r1.x, r1.y);
-          st.ray.time = r1.z;
+          const uint64_t word = load_ray(a.rays, id, st.ray);
           // The caller supplies the generator state and the materials' rejection loops are unbounded: xoroshiro64*
           // never leaves state 0, so the state is mended before anything can draw from it (scatter_kernel's rule; a
           // zero word is marked BAD besides)
@@ -199,48 +184,19 @@ __global__ __launch_bounds__(K.blk) __attribute__((amdgpu_waves_per_eu(K.occ, 8)
       Rec h;
       if (!solid_light) h = hit_record<K.feat>(S, st.ray, b, sh.kind);
       else h = Rec{mk(0.f, 0.f, 0.f), mk(0.f, 0.f, 0.f), 0.0f, 0.0f, true, 0u};
-      // One body for every material (material.rs:42-165, light_source.rs:17-24), as path_kernel's
-      const uint32_t mt = sh.kind & 0xffu, mode = (sh.kind >> 8) & 0xfu;
-      const bool light = (K.feat & F_LIGHT) && mt == MT_LIGHT;
-      const bool lam = (K.feat & F_LAMBERT) && mt == MT_LAMBERT;
-      const bool met = (K.feat & F_METAL) && mt == MT_METAL;
-      const bool iso = (K.feat & F_ISO) && mt == MT_ISOTROPIC;
+      // the materials' one body (rtw_dev_shade.hpp), the rejection draw and unit() between its pieces
+      const MatKind kind = mat_kind<K.feat>(sh.kind);
       V3 rs = mk(0.f, 0.f, 0.f);
-      if (lam || met || iso) rs = rand_in_unit_sphere<K.alignbit_draws()>(st.rng);  // vec3.rs:101-108
-      const V3 ud = unit(lam ? rs : st.ray.d);                  // Lambertian: unit(rs); else unit(d_in)
-      V3 att = mk(1.f, 1.f, 1.f);                                 // Dielectric: attenuation (1,1,1)
-      if (met) {
-        att = ld3(sh.a);
-      } else if (light || lam || iso) {
-        if (mode == SM_SOLID) att = ld3(sh.a);  // SolidColor::value
-        else if ((K.feat & F_CHECKER) && mode == SM_CHECKER)
-          att = checker_odd(sh.param * h.p.x, sh.param * h.p.y, sh.param * h.p.z) ? ld3(sh.a) : ld3(sh.b);
-        else if ((K.feat & F_IMAGE) && mode == SM_IMAGE)
-          att = image_texel(S, __float_as_uint(sh.a[0]), __float_as_uint(sh.a[1]), __float_as_uint(sh.a[2]), h.u, h.v);
-        else if (K.feat & F_TEXGEN) att = tex_value<K.feat>(S, S.mats[h.mat].tex, h.u, h.v, h.p);
-      }
+      if (kind.lam || kind.met || kind.iso) rs = rand_in_unit_sphere<K.alignbit_draws()>(st.rng);  // vec3.rs:101-108
+      const V3 ud = unit(kind.lam ? rs : st.ray.d);  // Lambertian: unit(rs); else unit(d_in)
+      const V3 att = mat_attenuation<K.feat>(S, sh, kind, h, [&] { return ld3(sh.b); });
       V3 Tn = mk(0.f, 0.f, 0.f);  // the throughput after this segment (scattering materials)
-      if (light) {  // emit, no scatter
+      if (kind.light) {  // emit, no scatter
         L = mul(T0, att);
         done = true;
         end = (uint32_t)RTW_SAMPLE_END_NO_SCATTER;
       } else {
-        V3 dir = rs;  // Isotropic (material.rs:155-165): never absorbs
-        if (lam) {    // material.rs:42-56
-          dir = add(h.n, ud);
-          if (near_zero(dir)) dir = h.n;
-        } else if (met) {  // material.rs:78-95
-          dir = add(reflect(ud, h.n), scale(rs, sh.param));
-          done = !(dot(dir, h.n) > 0.0f);  // absorbed: emitted() is black
-        } else if (!iso && (K.feat & F_DIEL)) {  // Dielectric, material.rs:116-142
-          const float ratio = h.front ? sh.a[0] : sh.param;
-          const float r0 = h.front ? sh.a[1] : sh.a[2];
-          const float cos_t = fminf(dot(neg(ud), h.n), 1.0f);
-          const float sin_t = sqrtf(1.0f - cos_t * cos_t);
-          const bool cannot = (ratio * sin_t) > 1.0f;
-          if (cannot || reflectance(cos_t, r0) > gen_f32(st.rng)) dir = reflect(ud, h.n);
-          else dir = refract(ud, h.n, ratio);
-        }
+        const V3 dir = mat_direction<K.feat>(sh, kind, h, ud, rs, st.rng, done);  // done: absorbed
         const V3 T2 = mul(T0, att);  // x * 1.0f == x: the Dielectric's T is unchanged
         // an absorbed Metal ray returns emitted() = black, which the recursion's parents multiply by their
         // attenuations: T * 0, not a constant 0 (path_kernel)

@@ -8,8 +8,11 @@
 # .Ltmp<n>), with the padding in front of a comment, which moves with a label's length.
 # Compares the kernels both revisions have and lists those only one of them has ("only in REV") separately: a revision
 # that adds or retires kernels is still compared on the rest.
-# Prints "identical N/N" per unit, or the first differing kernel and the head of its diff; exit status 1 if any kernel
-# both revisions have differs.
+# Prints "identical N/N" per unit, or every kernel that differs with what differs in it: "order only" when its resource
+# comment lines (NumVgprs, NumSgprs, ScratchSize, Occupancy, LDSByteSize, codeLenInByte) and its count of every
+# instruction mnemonic are the same, so that only the order of instructions or comments moved; else the resource lines
+# and mnemonic counts that changed, and the head of the first such kernel's diff.  Exit status 1 if any kernel both
+# revisions have differs.
 set -e
 [ $# -eq 2 ] || { echo "usage: $0 REV_A REV_B" >&2; exit 2; }
 ROOT="$(git -C "$(dirname "$0")" rev-parse --show-toplevel)"
@@ -27,7 +30,7 @@ for side in a b; do
 done
 wait
 python3 - "$TMP" "$1" "$2" <<'PY'
-import difflib, re, sys
+import collections, difflib, re, sys
 tmp, rev_a, rev_b = sys.argv[1:4]
 
 def kernels(path):
@@ -49,6 +52,12 @@ def kernels(path):
                      if not l.startswith(('\t.section\t.text', '\t.text', '\t.p2alignl ', '\t.fill '))]
     return out
 
+# a kernel's resource comment lines by name, and how often each instruction mnemonic occurs in it
+RES = re.compile(r'; (NumVgprs|NumSgprs|ScratchSize|Occupancy|LDSByteSize|codeLenInByte)\b')
+def profile(lines):
+    res = {m.group(1): l[2:] for l in lines for m in [RES.match(l)] if m}
+    return res, collections.Counter(l.split()[0] for l in lines if l[:1] == '\t' and l[1:2] not in ('', '.', ';'))
+
 bad = 0
 for unit in ('main', 'mesh'):
     a, b = kernels(f'{tmp}/a.{unit}.s'), kernels(f'{tmp}/b.{unit}.s')
@@ -62,8 +71,17 @@ for unit in ('main', 'mesh'):
               f'{sum(len(a[n]) for n in shared)} lines)')
         continue
     bad = 1
-    same = sum(a[n] == b[n] for n in shared)
-    print(f'{unit} unit: identical {same}/{len(shared)}; first differing kernel: {diff}')
-    print('\n'.join(list(difflib.unified_diff(a[diff], b[diff], rev_a, rev_b, lineterm='', n=1))[:40]))
+    differ = [n for n in shared if a[n] != b[n]]
+    print(f'{unit} unit: identical {len(shared) - len(differ)}/{len(shared)}; {len(differ)} differ:')
+    first = None
+    for n in differ:
+        (ra, oa), (rb, ob) = profile(a[n]), profile(b[n])
+        what = [f'{ra.get(k, k)} -> {rb.get(k, k)}' for k in sorted(set(ra) | set(rb)) if ra.get(k) != rb.get(k)]
+        what += [f'{m} {oa[m]} -> {ob[m]}' for m in sorted(set(oa) | set(ob)) if oa[m] != ob[m]]
+        print(f'  {n}: ' + ('; '.join(what) if what else 'order only'))
+        first = first or (n if what else None)
+    if first:
+        print(f'first changed kernel: {first}')
+        print('\n'.join(list(difflib.unified_diff(a[first], b[first], rev_a, rev_b, lineterm='', n=1))[:40]))
 sys.exit(bad)
 PY
