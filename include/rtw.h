@@ -442,6 +442,18 @@ int rtw_diag_sweep(int fn, uint32_t lo, uint32_t hi, uint64_t* counts, uint32_t*
 /* Diagnostics (host only, no device): the host's RN(1 / b) that the camera's u, v divisions use
  * (rtw_render*: b = w - 1, h - 1), over n values; exact for integer-valued b in [1, 2^24). */
 int rtw_diag_recip(uint32_t n, const float* b, float* out);
+/* Diagnostics: the per-tile lists a render of (cam, w x h) on `device` builds for its camera rays (the 1024-lane
+ * sphere kernel's start ring): per 8x8 tile of the frame, in tile order, 8 words = 16 halfwords, a count
+ * and then that many BVH primitive indices in ascending order (halfword 0 = 0xFFFF: more candidates than the cap,
+ * knob RTW_TILE_LIST_CAP).  Built whether or not a render of this camera would use them.  records holds cap_words
+ * words (>= 8 x tiles); *n_over (may be NULL) = the tiles on overflow; prim_keys (may be NULL) receives the DFS key
+ * (rtw_hit::key) of BVH primitive k for k < min(cap_keys, n).  Returns n, the BVH's primitive count, or an error. */
+int rtw_diag_tile_lists(rtw_scene* s, int device, const rtw_camera* cam, uint32_t w, uint32_t h, uint32_t* records,
+                        uint64_t cap_words, uint32_t* n_over, uint32_t* prim_keys, uint32_t cap_keys);
+/* Diagnostics (host only, no device): the lists' beam test (csrc/rtw_tile_beam.h) for one tile of a w x h frame and
+ * one box: 1 = a camera ray of the tile may meet the box, 0 = none can, < 0 an error. */
+int rtw_diag_tile_beam(const rtw_camera* cam, uint32_t w, uint32_t h, uint32_t tile, const float* box_lo,
+                       const float* box_hi);
 
 /* console_app/src/main.rs:68-90 tonemap: sqrt(sum/spp), clamp [0, 0.999], u8(255.999*c). */
 int rtw_tonemap(const float* rgb_sum, uint32_t n_pixels, uint32_t spp, uint8_t* rgb8);

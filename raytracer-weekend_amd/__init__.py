@@ -190,6 +190,9 @@ _SIGS = {
     "rtw_tonemap": (C.c_int, [_F, C.c_uint32, C.c_uint32, _U8]),
     "rtw_diag_libm": (C.c_int, [C.c_int, C.c_uint32, _F, _F, _F]),
     "rtw_diag_recip": (C.c_int, [C.c_uint32, _F, _F]),
+    "rtw_diag_tile_lists": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(rtw_camera), C.c_uint32, C.c_uint32, _U32,
+                                      C.c_uint64, _U32, _U32, C.c_uint32]),
+    "rtw_diag_tile_beam": (C.c_int, [C.POINTER(rtw_camera), C.c_uint32, C.c_uint32, C.c_uint32, _F, _F]),
     "rtw_diag_sweep": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), _U32, C.c_uint32]),
     "rtw_scene_preset": (C.c_int, [C.c_void_p, C.c_char_p, C.c_float, C.c_uint64, C.c_char_p,
                                    C.POINTER(rtw_camera), _F]),
@@ -767,6 +770,31 @@ def diag_recip(b) -> np.ndarray:
     out = np.empty_like(b)
     _check(lib().rtw_diag_recip(len(b), _fp(b), _fp(out)))
     return out
+
+
+def diag_tile_beam(cam, w: int, h: int, tile: int, box_lo, box_hi) -> bool:
+    """The tile lists' beam test for one tile and one box (host only): may a camera ray of the tile meet the box?"""
+    lo, hi = _fa(box_lo), _fa(box_hi)
+    rc = lib().rtw_diag_tile_beam(C.byref(cam.c), w, h, tile, _fp(lo), _fp(hi))
+    if rc < 0:
+        _check(rc)
+    return bool(rc)
+
+
+def diag_tile_lists(scene, cam, w: int, h: int, device: int = 0):
+    """rtw_diag_tile_lists -> (per tile a list of BVH primitive indices, or None for a tile on overflow; the overflow
+    count; the DFS key of every BVH primitive, by index)."""
+    nt = n_tiles(w, h)
+    rec = np.zeros(nt * 8, np.uint32)
+    over = C.c_uint32()
+    keys = np.zeros(65536, np.uint32)
+    n = lib().rtw_diag_tile_lists(scene._p, device, C.byref(cam.c), w, h, _up(rec), rec.size, C.byref(over),
+                                  _up(keys), keys.size)
+    if n < 0:
+        _check(n)
+    half = rec.view(np.uint16).reshape(nt, 16)
+    lists = [None if r[0] == 0xFFFF else [int(x) for x in r[1:1 + int(r[0])]] for r in half]
+    return lists, int(over.value), keys[:n]
 
 
 def tile_partition(w: int, h: int, n_parts: int, part: int):

@@ -196,6 +196,15 @@ class World {
     check(rtw_camera_rays(s_, device, &cam.c, w, h, spp, seed, first, n, rays.data(), st));
     return rays;
   }
+  // diagnostics: the per-tile lists a render of (cam, w x h) builds for its camera rays (rtw_diag_tile_lists): 8 words
+  // per 8x8 tile, in tile order; *n_over (or nullptr) = the tiles on overflow
+  std::vector<uint32_t> tile_lists(const Camera& cam, uint32_t w, uint32_t h, int device = -1,
+                                   uint32_t* n_over = nullptr) const {
+    std::vector<uint32_t> rec((size_t)((w + 7u) / 8u) * ((h + 7u) / 8u) * 8u);
+    const int n = rtw_diag_tile_lists(s_, device, &cam.c, w, h, rec.data(), rec.size(), n_over, nullptr, 0);
+    if (n < 0) check(n);
+    return rec;
+  }
   // Material::scatter + emitted for every (ray, hit record) pair (lib.rs:102-116): the scattered rays replace `rays`
   std::vector<Scatter> scatter_rays(std::vector<Ray>& rays, const std::vector<Hit>& hits, Color background,
                                     int device = -1, rtw_stats* st = nullptr) const {

@@ -596,6 +596,7 @@ int64_t rtw_scene_info(const rtw_scene* s, int what) {
     case 15: return (int64_t)llround(1000.0 * (double)sc.flat.far_d0);
     case 16: case 17: case 18: case 19: case 20: case 21: case 22: case 23:
       return selected_kernel_info(sc, what - 16);
+    case 24: case 25: return last_render_lists(const_cast<Scene&>(sc), what - 24);
     case 4: return (int64_t)sc.flat.depth;
     case 5: return (int64_t)sc.flat.always.size();
     case 6: return (int64_t)sc.flat.insts.size();

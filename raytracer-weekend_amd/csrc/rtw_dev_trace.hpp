@@ -286,11 +286,18 @@ constexpr bool far_kernel_feat(uint32_t feat) {
 }
 // C16: the kernel's LDS stack holds 16-bit entries (the LDS-node and S16 walks), else 32-bit ones (stk); trace_far
 // borrows the lane's column.  A lane whose segment needs the far-origin walk takes it here, instead of the main walk.
-template <bool COUNT, uint32_t FEAT, int STACK = 1, int BLK = BLOCK, bool C16 = false, int NCAP = 0>
+// RING (the 1024-lane sphere kernel's start ring, path_kernel): `start` is what the lane's ring entry decided for this
+// segment -- a primitive index (the segment's closest hit: the lane tests that primitive alone, so ts.b gets the same
+// t from the same test, and takes no root), -1 (a miss: no test, no root) or -3 (undecided, and every later segment: the
+// always list and the walk as ever).  One loop serves all three, the index per lane, so a decided lane adds no
+// instruction stream of its own.
+template <bool COUNT, uint32_t FEAT, int STACK = 1, int BLK = BLOCK, bool C16 = false, int NCAP = 0, bool RING = false>
 __device__ __forceinline__ void trace_begin(const DevScene& S, const Ray& r, TraceState& ts, uint32_t* cnt,
                                             uint64_t seg, uint16_t* stk16 = nullptr, int32_t* stk = nullptr,
-                                            uint32_t* err = nullptr, const float4* lnodes = nullptr) {
+                                            uint32_t* err = nullptr, const float4* lnodes = nullptr,
+                                            int32_t start = -3) {
   ts.b = Best{INFINITY, 0u, -1, 0.0f, 0.0f};
+  const bool decided = RING && start != -3;
   // list-mode worlds of rects only (the F_BOXES | F_LIST kernel)
   constexpr bool RECT_LIST = (FEAT & F_LIST) && (FEAT & F_RECT) && !(FEAT & (F_SPHERE | F_MSPHERE | F_TRI | F_MEDIUM));
   if constexpr (RECT_LIST) {
@@ -312,6 +319,17 @@ __device__ __forceinline__ void trace_begin(const DevScene& S, const Ray& r, Tra
         cur = inst;
       }
       test_prim<COUNT, FEAT, true, true>(S, pi, lr, ts.b, cnt, seg);
+    }
+  } else if constexpr (RING) {
+    // (measured against a second form -- every lane the scalar always loop, then the lanes whose winner is a BVH
+    // primitive one more test of their own -- this one loop was 1.6% faster: profiles/r08/experiments)
+    const SphRcp rq = sph_rcp(r);
+    const uint32_t n = decided ? (start >= 0 ? 1u : 0u) : S.n_always;
+    for (uint32_t k = 0; __any(k < n); ++k) {
+      if (k < n) {
+        const uint32_t pi = decided ? (uint32_t)start : uload(S.always + k);
+        test_prim<COUNT, FEAT, false, false>(S, pi, r, ts.b, cnt, seg, &rq);
+      }
     }
   } else {
     constexpr bool SPH_ONLY = (FEAT & (F_RECT | F_TRI | F_MEDIUM | F_INST)) == 0 && (FEAT & (F_SPHERE | F_MSPHERE));
@@ -344,7 +362,7 @@ __device__ __forceinline__ void trace_begin(const DevScene& S, const Ray& r, Tra
       const float ty = fabsf(r.o.y - mid.y) + half.y;
       const float tz = fabsf(r.o.z - mid.z) + half.z;
       const float D2 = tx * tx + ty * ty + tz * tz;  // the farthest corner of the BVH box, squared
-      const bool far = D2 > mid.w;
+      const bool far = D2 > mid.w && !decided;  // (a decided start's origin is near: the host's condition for lists)
       if (__any(far)) {
         bool need = false;
         float delta = 0.0f;
@@ -384,7 +402,7 @@ __device__ __forceinline__ void trace_begin(const DevScene& S, const Ray& r, Tra
   } else {
     asm volatile("" : "+v"(root));
   }
-  ts.node = walk ? root : -1;
+  ts.node = (walk && !decided) ? root : -1;
   ts.pend = 0;
   ts.sp = 0;
   ts.on = true;

@@ -263,6 +263,14 @@ struct RenderArgs {
   int32_t* spill;                // traversal stack entries beyond the LDS stack: [depth][lane]
   uint32_t spill_depth;          // entries per lane (0 = the LDS stack covers the tree's bound)
   uint32_t spill_lanes;          // resident lanes of the launch (stride between levels)
+  // (appended: the kernels that do not read it keep their argument offsets)
+  const uint32_t* tile_lists;    // per global 8x8 tile id one TILE_LIST_WORDS record (tile_list_kernel), or nullptr: this
+                                 // render resolves no camera ray from the lists (path_kernel, K.ldsn_ring())
 };
+
+// A tile's list of the BVH primitives a camera ray of the tile may hit (rtw_tile_beam.h): 16 halfwords = a count,
+// then up to TILE_LIST_MAX primitive indices in ascending order; count TILE_LIST_OVER = more candidates than the cap,
+// the tile's camera rays walk the tree
+constexpr uint32_t TILE_LIST_WORDS = 8, TILE_LIST_MAX = 15, TILE_LIST_OVER = 0xFFFFu;
 
 }  // namespace rtw

@@ -822,6 +822,12 @@ int flatten(Scene& s) {
     f.depth = bb.max_depth;
   }
   for (const Leaf& L : rest) f.prims.push_back(L.p);
+  // the BVH primitives' padded boxes as the tree was built over them, indexed like prims[] (the per-tile lists of
+  // camera rays, rtw_tile_beam.h): (lo, 0), (hi, 0)
+  f.pboxes.clear();
+  for (const Leaf& L : rest)
+    f.pboxes.insert(f.pboxes.end(), {L.wbox.lo[0], L.wbox.lo[1], L.wbox.lo[2], 0.0f, L.wbox.hi[0], L.wbox.hi[1],
+                                     L.wbox.hi[2], 0.0f});
   for (const Leaf& L : huge) {  // the kernels rely on this: always[k] = prims.size() - always.size() + k
     f.always.push_back((uint32_t)f.prims.size());
     f.prims.push_back(L.p);

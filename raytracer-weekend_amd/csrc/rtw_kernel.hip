@@ -1,6 +1,6 @@
 // rtw_kernel.hip — what of the gfx950 path-tracing megakernel's host side needs the device compiler: the kernels
-// that are no templates (reduce_kernel, unpack_tiles_kernel, the libm and reciprocal diagnostics, with the two calls
-// that launch the latter), the tuning knobs, pick_kernel (which path-kernel variant a scene runs) and the launches
+// that are no templates (reduce_kernel, unpack_tiles_kernel, tile_list_kernel with its diagnostic calls, the libm and
+// reciprocal diagnostics, with the two calls that launch the latter), the tuning knobs, pick_kernel (which path-kernel variant a scene runs) and the launches
 // (enqueue_render, enqueue_hit_rays, enqueue_sample_rays, enqueue_scatter_rays, enqueue_camera_rays, enqueue_unpack),
 // which share one cache of resident grids (resident_blocks), the walk's tuning (tune_walk) and the one-record-per-lane
 // queries' launch (launch_query).  The
@@ -63,6 +63,7 @@
 #include "rtw_scene.hpp"
 #include "rtw_variants.hpp"
 #include "rtw_shade_kernel.hpp"
+#include "rtw_tile_beam.h"
 
 namespace rtw {
 namespace dev {
@@ -102,6 +103,56 @@ __global__ void unpack_tiles_kernel(uint32_t w, uint32_t h, uint32_t tiles_x, co
   const uint32_t i = (tile % tiles_x) * 8u + (lane & 7u), row = (tile / tiles_x) * 8u + (lane >> 3);
   if (i >= w || row >= h) return;
   for (int c = 0; c < 3; ++c) img[((size_t)row * w + i) * 3 + c] = packed[(size_t)g * 3 + c];
+}
+
+// The per-tile lists of camera rays (path_kernel's ring, K.ldsn_ring()): one thread per 8x8 tile of the
+// frame, global tile id = thread id.  The workgroup brings the BVH primitives' padded boxes into the camera's frame
+// TILE_LIST_CHUNK at a time (LDS), then every thread runs the beam test of its tile against them in index order and
+// keeps the candidates: a 32-B record per tile (TILE_LIST_WORDS), TILE_LIST_OVER past `cap` candidates.  n_over counts
+// the tiles on overflow.
+constexpr uint32_t TILE_LIST_BLOCK = 64, TILE_LIST_CHUNK = 256;
+struct TileListArgs {
+  DevCamera cam;
+  uint32_t w, h, n_tiles, n_bvh, cap;
+  const float4* boxes;  // per BVH prim (lo, 0), (hi, 0)
+  uint32_t* lists;
+  uint32_t* n_over;
+};
+__global__ __launch_bounds__(TILE_LIST_BLOCK) void tile_list_kernel(TileListArgs a) {
+  __shared__ BeamBox cbox[TILE_LIST_CHUNK];
+  const uint32_t tile = blockIdx.x * TILE_LIST_BLOCK + threadIdx.x;
+  const BeamCamera C = beam_camera(a.cam.origin, a.cam.u, a.cam.v, a.cam.llc, a.cam.horizontal, a.cam.vertical,
+                                   a.cam.lens_radius);
+  const BeamTile T = beam_tile(C, a.w, a.h, tile < a.n_tiles ? tile : 0u);
+  uint32_t rec[TILE_LIST_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
+  uint32_t n = 0;
+  for (uint32_t base = 0; base < a.n_bvh; base += TILE_LIST_CHUNK) {
+    const uint32_t m = min(TILE_LIST_CHUNK, a.n_bvh - base);
+    __syncthreads();
+    for (uint32_t k = threadIdx.x; k < m; k += TILE_LIST_BLOCK) {
+      const float4 lo = a.boxes[2u * (base + k)], hi = a.boxes[2u * (base + k) + 1u];
+      const float l[3] = {lo.x, lo.y, lo.z}, h[3] = {hi.x, hi.y, hi.z};
+      cbox[k] = beam_box(C, l, h);
+    }
+    __syncthreads();
+    for (uint32_t k = 0; k < m; ++k) {
+      if (beam_may_hit(C, T, cbox[k])) {
+        ++n;  // halfword n of the record (while it fits)
+        if (n <= TILE_LIST_MAX) {
+          const uint32_t v = (base + k) << ((n & 1u) * 16u);
+#pragma unroll
+          for (uint32_t q = 0; q < TILE_LIST_WORDS; ++q) rec[q] |= (n >> 1) == q ? v : 0u;
+        }
+      }
+    }
+  }
+  if (tile >= a.n_tiles) return;
+  const bool over = n > a.cap;
+  rec[0] = over ? TILE_LIST_OVER : (rec[0] | n);
+  uint4* o = reinterpret_cast<uint4*>(a.lists + (size_t)tile * TILE_LIST_WORDS);
+  o[0] = make_uint4(rec[0], rec[1], rec[2], rec[3]);
+  o[1] = make_uint4(rec[4], rec[5], rec[6], rec[7]);
+  if (over) atomicAdd(a.n_over, 1u);
 }
 
 // Diagnostics (rtw_diag_libm): the render path's f32 transcendentals over arrays.
@@ -181,6 +232,8 @@ static Knobs read_knobs() {
   k.leaf16 = knob("RTW_LEAF16");
   k.regen_min = knob("RTW_REGEN_MIN");
   k.pass_log2 = knob("RTW_PASS_LOG2");
+  k.tile_lists = knob("RTW_TILE_LISTS");
+  k.tile_list_cap = knob("RTW_TILE_LIST_CAP");
   const char* v = getenv("RTW_VERBOSE");
   k.verbose = v && atoi(v);
   return k;
@@ -274,6 +327,20 @@ int64_t selected_kernel_info(const Scene& s, int field) {
   const KernelCfg k = path_kernel_variant(s.flat, read_knobs()).cfg;
   const int64_t v[8] = {k.stack, k.spill, k.occ, k.feat, k.blk, k.ncap, k.half, k.s16};
   return field >= 0 && field < 8 ? v[field] : -1;
+}
+
+// rtw_scene_info 24, 25: whether the last render on the scene's first device copy resolved its camera rays from tile
+// lists, and how many of the frame's tiles were on overflow (waits for that render)
+int64_t last_render_lists(Scene& s, int field) {
+  DeviceCopy* c = find_copy(s, -1);
+  if (!c) return 0;
+  if (field == 0 || !c->lists_used) return field == 0 ? (int64_t)c->lists_used : 0;
+  DeviceGuard g;
+  uint32_t n = 0;
+  if (hipSetDevice(c->phys) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+      hipMemcpy(&n, c->lists_count, sizeof n, hipMemcpyDeviceToHost) != hipSuccess)
+    return -1;
+  return (int64_t)n;
 }
 
 // The resident capacity of kernel fn in blocks of `block` lanes on c's device (blocks per CU x CUs): the persistent
@@ -390,7 +457,8 @@ struct LaunchTuning {
 static LaunchTuning tune_launch(const Knobs& kn, const Flat& flat, const KernelCfg& k, int grid) {
   LaunchTuning a;
   a.walk = tune_walk(kn, flat, k, grid);
-  // see trace_run (measured best of 4..16 on jumpy-balls); tuning knob RTW_QUOTA16 (1..16)
+  // see trace_run (measured best of 4..16 on jumpy-balls); tuning knob RTW_QUOTA16 (1..16); run_passes lowers it for
+  // a full-size pass whose camera rays are resolved from the tile lists
   a.quota16 = (uint32_t)std::min(16, std::max(1, kn.quota16.get(12)));
   // whole wave-loads of ids only (batch_ids): the start ring makes 64 path starts from 64 consecutive ids of a batch.
   // The 1024-lane LDS-node kernel and the BVH-less list kernels: 1024 ids per atomic (a shorter end-of-frame
@@ -457,6 +525,11 @@ static int run_passes(Scene& sc, DeviceCopy& c, RenderArgs& a, const Knobs& kn, 
     a.slot_base = base;
     a.n_paths = (uint64_t)ns * per_slot;
     a.batch = kn.batch.set ? t.batch : pass_batch(t.batch, a.n_paths, waves);
+    // A pass whose camera rays are resolved from the tile lists walks bounce rays only, which finish further apart,
+    // and the quota is a share of the lanes that walk (path_kernel): 8/16 measured best of 4..14 at 1080p, +3% over
+    // 12.  A small pass (one pass_batch gave smaller batches: its end-of-pass tail counts) keeps 12: jumpy-400 lost 5%
+    // at 8 (profiles/r08/experiments).
+    if (!kn.quota16.set) a.quota16 = (a.tile_lists && a.batch == t.batch) ? 8u : t.quota16;
     if (base) HIPCHK(hipMemsetAsync(a.queue, 0, DISP * DISP_STRIDE * sizeof(unsigned long long), stream),
                      "hipMemsetAsync(queue)");
     hipEvent_t* ke = c.kev[c.kev_head];
@@ -474,6 +547,68 @@ static int run_passes(Scene& sc, DeviceCopy& c, RenderArgs& a, const Knobs& kn, 
   return RTW_OK;
 }
 
+// The per-tile lists serve a render when every camera ray starts from a *near* origin, the ones the BVH's sphere boxes
+// are padded for (rtw_flatten.cpp far_bound: D(o) <= D0): D is convex in o, so the four corners of the lens' bounding
+// square decide for the whole lens.  In double, with slack for the kernel's f32 origin.
+static bool lens_is_near(const Flat& flat, const rtw_camera& cam) {
+  if (!flat.far_check) return false;
+  const DevFar& F = flat.far;
+  const double R = fabs((double)cam.lens_radius);
+  for (int q = 0; q < 4; ++q) {
+    double D2 = 0.0;
+    for (int k = 0; k < 3; ++k) {
+      const double o = (double)cam.origin[k] + ((q & 1) ? R : -R) * (double)cam.u[k] + ((q & 2) ? R : -R) * (double)cam.v[k];
+      const double t = fabs(o - (double)F.mid[k]) + (double)F.half[k];
+      D2 += t * t;
+    }
+    if (!(D2 * (1.0 + 1.0e-6) <= (double)F.d2)) return false;  // (a NaN camera: off)
+  }
+  return true;
+}
+
+static dev::TileListArgs tile_list_args(const rtw_camera& cam, uint32_t w, uint32_t h, uint32_t n_bvh, uint32_t cap) {
+  dev::TileListArgs t;
+  memset(&t, 0, sizeof t);
+  memcpy(t.cam.origin, cam.origin, sizeof t.cam.origin);
+  memcpy(t.cam.llc, cam.lower_left_corner, sizeof t.cam.llc);
+  memcpy(t.cam.horizontal, cam.horizontal, sizeof t.cam.horizontal);
+  memcpy(t.cam.vertical, cam.vertical, sizeof t.cam.vertical);
+  memcpy(t.cam.u, cam.u, sizeof t.cam.u);
+  memcpy(t.cam.v, cam.v, sizeof t.cam.v);
+  t.cam.lens_radius = cam.lens_radius;
+  t.w = w;
+  t.h = h;
+  t.n_tiles = (uint32_t)(((uint64_t)(w + 7u) / 8u) * ((h + 7u) / 8u));
+  t.n_bvh = n_bvh;
+  t.cap = cap;
+  return t;
+}
+
+// Builds the frame's tile records on `stream` into `lists` (TILE_LIST_WORDS per tile of the frame) and zeroes, then
+// counts, the tiles on overflow in *n_over.  A render rebuilds them on every call: camera and size change from frame
+// to frame in real use, and the build is a few tens of microseconds (profiles/r08/experiments).
+static int enqueue_tile_lists(Scene& sc, DeviceCopy& c, const rtw_camera& cam, uint32_t w, uint32_t h, uint32_t cap,
+                              uint32_t* lists, uint32_t* n_over, hipStream_t stream) {
+  dev::TileListArgs t = tile_list_args(cam, w, h, sc.flat.far.n_bvh, cap);
+  t.boxes = static_cast<const float4*>(c.pboxes.p);
+  t.lists = lists;
+  t.n_over = n_over;
+  HIPCHK(hipMemsetAsync(n_over, 0, sizeof(uint32_t), stream), "hipMemsetAsync(tile-list counter)");
+  hipLaunchKernelGGL(dev::tile_list_kernel, dim3((t.n_tiles + dev::TILE_LIST_BLOCK - 1u) / dev::TILE_LIST_BLOCK),
+                     dim3(dev::TILE_LIST_BLOCK), 0, stream, t);
+  HIPCHK(hipGetLastError(), "tile_list_kernel launch");
+  return RTW_OK;
+}
+// whether a render of `cam` resolves its camera rays from tile lists, and the cap it builds them with
+static bool tile_lists_on(const Scene& sc, const DeviceCopy& c, const rtw_camera& cam, uint32_t* cap) {
+  const Knobs kn = read_knobs();
+  *cap = (uint32_t)std::min((int)TILE_LIST_MAX, std::max(1, kn.tile_list_cap.get((int)TILE_LIST_MAX)));
+  const uint32_t n_bvh = sc.flat.far.n_bvh;
+  return kn.tile_lists.get(1) != 0 && path_kernel_variant(sc.flat, kn).cfg.ldsn_ring() && c.pboxes.p &&
+         c.lists_count && n_bvh > 0 && n_bvh < TILE_LIST_OVER && sc.flat.pboxes.size() == (size_t)n_bvh * 8u &&
+         lens_is_near(sc.flat, cam);
+}
+
 int enqueue_render(Scene& sc, DeviceCopy& c, const Frame& f, const TileSet& ts, float* d_out, hipStream_t stream,
                    uint32_t flags, hipEvent_t ev0, hipEvent_t ev1) {
   // an earlier render on this device (one the caller did not wait on) tripped the guard: report it now
@@ -482,12 +617,36 @@ int enqueue_render(Scene& sc, DeviceCopy& c, const Frame& f, const TileSet& ts, 
   if (int e = check_shutter(*f.cam, sc.flat)) return e;
   RenderArgs a = frame_args(c, f, ts, d_out);
   const Knobs kn = read_knobs();
+  c.lists_used = 0;
   HIPCHK(hipMemsetAsync(c.counters, 0, COUNTER_WORDS * sizeof(unsigned long long), stream), "hipMemsetAsync");
   if (ev0) HIPCHK(hipEventRecord(ev0, stream), "hipEventRecord");
   if (ts.n && (f.spp == 0 || f.max_depth == 0)) {  // lib.rs:83 loops 0 times / :98 returns black
     size_t n = a.packed_out ? (size_t)ts.n * 64 * 3 : (size_t)f.w * f.h * 3;
     HIPCHK(hipMemsetAsync(d_out, 0, n * sizeof(float), stream), "hipMemsetAsync(out)");
   } else if (ts.n) {
+    // the frame's tile lists first (records by global tile id: every tile subset and pass reads the same table)
+    uint32_t cap = 0;
+    c.lists_used = tile_lists_on(sc, c, *f.cam, &cap) ? 1u : 0u;
+    if (c.lists_used) {  // (the buffer is grown once, like the sample buffer)
+      // The build measured 0.2 ms at 1080p (profiles/r08/experiments), above the 0.1 ms a rebuild per call was
+      // allowed: the records are kept for the (camera, size, cap) they were built for, compared field by field, and a
+      // render on the same stream with the same ones reuses them (an animation's frames rebuild, a frame's tile
+      // subsets, passes and repeats do not)
+      DeviceCopy::ListsKey& key = c.lists_key;
+      const bool same = key.valid && key.w == f.w && key.h == f.h && key.cap == cap && key.stream == stream &&
+                        memcmp(&key.cam, f.cam, sizeof key.cam) == 0;
+      if (!same) {
+        key.valid = false;
+        if (int e = grow(c.tile_lists, (size_t)f.tiles() * TILE_LIST_WORDS * sizeof(uint32_t))) return e;
+        if (int e = enqueue_tile_lists(sc, c, *f.cam, f.w, f.h, cap, static_cast<uint32_t*>(c.tile_lists.p),
+                                       c.lists_count, stream))
+          return e;
+        key.cam = *f.cam;
+        key.w = f.w; key.h = f.h; key.cap = cap; key.stream = stream;
+        key.valid = true;
+      }
+      a.tile_lists = static_cast<const uint32_t*>(c.tile_lists.p);
+    }
     if (int e = run_passes(sc, c, a, kn, ts.n, flags & RTW_FLAG_COUNT_TRAVERSAL, stream)) return e;
   }
   if (ev1) HIPCHK(hipEventRecord(ev1, stream), "hipEventRecord");
@@ -647,6 +806,44 @@ int rtw_diag_libm(int fn, uint32_t n, const float* a, const float* b, float* out
   if (hipGetLastError() != hipSuccess || hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost) != hipSuccess)
     return fail(RTW_ENODEV, "libm_kernel");
   return RTW_OK;
+}
+
+int rtw_diag_tile_lists(rtw_scene* s, int device, const rtw_camera* cam, uint32_t w, uint32_t h, uint32_t* records,
+                        uint64_t cap_words, uint32_t* n_over, uint32_t* prim_keys, uint32_t cap_keys) {
+  if (!s || !cam || !records) return fail(RTW_EINVAL, "NULL argument");
+  if (!s->s.committed) return fail(RTW_ESTATE, "scene not committed");
+  if (int e = check_image_min(w, h)) return e;
+  if (int e = check_image_max(w, h)) return e;
+  DeviceCopy* c = need_copy(s->s, device);
+  if (!c) return RTW_ENODEV;
+  const uint32_t n_bvh = s->s.flat.far.n_bvh;
+  if (!c->pboxes.p || n_bvh == 0 || n_bvh >= TILE_LIST_OVER || s->s.flat.pboxes.size() != (size_t)n_bvh * 8u)
+    return fail(RTW_EINVAL, "the scene has no sphere BVH of under %u primitives: no tile lists", TILE_LIST_OVER);
+  const uint64_t words = (uint64_t)((w + 7u) / 8u) * ((h + 7u) / 8u) * TILE_LIST_WORDS;
+  if (cap_words < words) return fail(RTW_EINVAL, "records: %llu words needed", (unsigned long long)words);
+  const Knobs kn = read_knobs();
+  const uint32_t cap = (uint32_t)std::min((int)TILE_LIST_MAX, std::max(1, kn.tile_list_cap.get((int)TILE_LIST_MAX)));
+  DeviceGuard g;
+  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
+  DiagBuf<uint32_t> lists, over;
+  if (!lists.alloc(words) || !over.alloc(1)) return fail(RTW_ENOMEM, "hipMalloc(tile lists)");
+  if (int e = enqueue_tile_lists(s->s, *c, *cam, w, h, cap, lists.p, over.p, nullptr)) return e;
+  uint32_t no = 0;
+  if (hipMemcpy(records, lists.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(&no, over.p, sizeof no, hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(RTW_ENODEV, "tile_list_kernel");
+  if (n_over) *n_over = no;
+  for (uint32_t k = 0; prim_keys && k < std::min(cap_keys, n_bvh); ++k) prim_keys[k] = s->s.flat.prims[k].key;
+  return (int)n_bvh;
+}
+
+int rtw_diag_tile_beam(const rtw_camera* cam, uint32_t w, uint32_t h, uint32_t tile, const float* box_lo,
+                       const float* box_hi) {
+  if (!cam || !box_lo || !box_hi) return fail(RTW_EINVAL, "NULL argument");
+  if (int e = check_image_min(w, h)) return e;
+  const BeamCamera C = beam_camera(cam->origin, cam->u, cam->v, cam->lower_left_corner, cam->horizontal, cam->vertical,
+                                   cam->lens_radius);
+  return beam_may_hit(C, beam_tile(C, w, h, tile), beam_box(C, box_lo, box_hi)) ? 1 : 0;
 }
 
 int rtw_diag_sweep(int fn, uint32_t lo, uint32_t hi, uint64_t* counts, uint32_t* bad, uint32_t cap) {

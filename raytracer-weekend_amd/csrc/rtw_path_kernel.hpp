@@ -71,16 +71,23 @@ __device__ __forceinline__ void fill_start_args(const RenderArgs& a, StartArgs& 
 }
 
 // start_path (below) in two halves, for the start ring's 7-word entry (path_kernel SRING, K.ldsn_ring()): start_make
-// is everything up to the time draw -- the scaled lens sample rd, the direction d and the generator's state before
-// that draw -- and start_take the rest from those: the origin (the lens offset again, from the same operands), the
-// time draw, T, depth and the id.  The same f32 operations on the same inputs as start_path's, so every bit of the
-// start is the same.  (A copy, not start_path's own body: with start_path written as the two halves back to back
+// is everything up to the time draw -- the scaled lens sample rd, the image coordinates u, v (and the direction d from
+// them) and the generator's state before that draw -- and start_take the rest from those: the origin (the lens offset
+// again, from the same operands), the direction, the time draw, T, depth and the id.  The same f32 operations on the
+// same inputs as start_path's, so every bit of the start is the same.  (A copy, not start_path's own body: with start_path written as the two halves back to back
 // every other variant's register allocation moved -- VGPRs, scratch and VALU count, scripts/isa_usage.sh.)
+// (The entry keeps u, v instead of d: start_take rebuilds d with start_make's own expression, the same operations in
+// the same order on the same bits, and the word this frees holds the start's first hit, below.)
 struct StartMade {
   float rdx, rdy;
+  float u, v;
   V3 d;
   uint64_t rng;
+  uint32_t tile;  // the 64 ids' global tile (wave-uniform: 64 consecutive ids are one sample of one tile)
 };
+// What a ring entry knows of its path's first segment (the per-tile lists, rtw_tile_beam.h): the closest hit's
+// primitive index (>= 0), START_MISS (nothing hit), or START_WALK (not decided: the segment walks the tree)
+constexpr int32_t START_MISS = -1, START_WALK = -3;
 template <bool FROM_LDS, bool AB>
 __device__ __forceinline__ bool start_make(const StartArgs& a, uint64_t pid, StartMade& m) {
   if constexpr (FROM_LDS) asm volatile("" ::: "memory");  // read the LDS copy here: no loop-invariant register copies
@@ -102,23 +109,62 @@ __device__ __forceinline__ bool start_make(const StartArgs& a, uint64_t pid, Sta
   const V3 off = add(scale(ld3(C.u), rd.x), scale(ld3(C.v), rd.y));
   m.rdx = rd.x;
   m.rdy = rd.y;
+  m.u = u;
+  m.v = v;
+  m.tile = tile;
   m.d = sub(sub(add(add(ld3(C.llc), scale(ld3(C.horizontal), u)), scale(ld3(C.vertical), v)), ld3(C.origin)), off);
   m.rng = rng;
   return i < a.w && row < a.h;
 }
 // (FENCE: the ring's take re-reads the LDS copy of the operands, as start_make does)
 template <bool FENCE, bool AB>
-__device__ __forceinline__ void start_take(const StartArgs& a, float rdx, float rdy, uint64_t rng, uint32_t pid,
-                                           PathState& st) {
+__device__ __forceinline__ void start_take(const StartArgs& a, float rdx, float rdy, float u, float v, uint64_t rng,
+                                           uint32_t pid, PathState& st) {
   if constexpr (FENCE) asm volatile("" ::: "memory");
   const DevCamera& C = a.cam;
   const V3 off = add(scale(ld3(C.u), rdx), scale(ld3(C.v), rdy));
   st.ray.o = add(ld3(C.origin), off);
+  st.ray.d = sub(sub(add(add(ld3(C.llc), scale(ld3(C.horizontal), u)), scale(ld3(C.vertical), v)), ld3(C.origin)), off);
   st.ray.time = gen_range<AB>(rng, C.time0, C.time1, a.time_span);
   st.rng = rng;
   st.T = mk(1.f, 1.f, 1.f);
   st.depth = a.max_depth;
   st.pid = pid;
+}
+
+// The ring's make step, after start_make: the first segment's closest hit from the tile's list (RenderArgs::tile_lists),
+// with all 64 lanes on.  Every lane finishes its camera ray as start_take will (the time drawn from a copy of the
+// generator's state, the origin from the same operands) and folds the always-list and the tile's list with the walks'
+// own test_prim and Best: the list holds every BVH primitive a camera ray of the tile can hit (rtw_tile_beam.h), the
+// fold is the walk's commutative one (min t, ties to the larger key), so the winner is the walk's.  The list's words
+// and the primitives' records come through scalar loads (the tile is wave-uniform).  START_WALK when the render has no
+// lists or the tile's list overflowed.
+template <bool COUNT, uint32_t FEAT, bool AB>
+__device__ __forceinline__ int32_t start_decide(const DevScene& S, const StartArgs& a, const uint32_t* lists,
+                                                const StartMade& m, uint32_t* cnt) {
+  if (!lists) return START_WALK;  // kernel-uniform
+  const uint32_t tile = (uint32_t)__builtin_amdgcn_readfirstlane((int)m.tile);
+  // (a caller's tile table may name a tile outside the frame: its ids are all off-image, and it has no record)
+  if (tile >= a.tiles_x * ((a.h + 7u) >> 3)) return START_WALK;
+  const uint32_t* const rec = lists + (size_t)tile * TILE_LIST_WORDS;
+  const uint32_t w0 = uload(rec);
+  const uint32_t n = w0 & 0xFFFFu;
+  if (n == TILE_LIST_OVER) return START_WALK;  // wave-uniform
+  const DevCamera& C = a.cam;
+  Ray r;
+  const V3 off = add(scale(ld3(C.u), m.rdx), scale(ld3(C.v), m.rdy));
+  r.o = add(ld3(C.origin), off);
+  r.d = m.d;
+  uint64_t g = m.rng;
+  r.time = gen_range<AB>(g, C.time0, C.time1, a.time_span);
+  const SphRcp rq = sph_rcp(r);
+  Best b = Best{INFINITY, 0u, -1, 0.0f, 0.0f};
+  for (uint32_t k = 0; k < S.n_always; ++k) test_prim<COUNT, FEAT, false, true>(S, uload(S.always + k), r, b, cnt, g, &rq);
+  for (uint32_t k = 1; k <= n; ++k) {  // halfword k of the record
+    const uint32_t pi = (uload(rec + (k >> 1)) >> ((k & 1u) * 16u)) & 0xFFFFu;
+    test_prim<COUNT, FEAT, false, true>(S, pi, r, b, cnt, g, &rq);
+  }
+  return b.prim;  // >= 0, or -1 = START_MISS
 }
 
 // LST_BLK > 0: also store T = 1, depth and the path id in the lane's LDS state rows (path_kernel LST), here
@@ -310,8 +356,9 @@ __global__ __launch_bounds__(K.blk) __attribute__((amdgpu_waves_per_eu(K.occ, 8)
   // Per lane slot: o, d, time, rng (2 words), pid (10 words, structure of arrays); rng = 0 marks an off-image id.
   // (the rect list kernel: its LDS is free and its VGPRs hold the generation.)
   // The 1024-lane LDS-node sphere kernel (K.ldsn_ring()) has 1.75 KB per wave beside its stack and node table: a 7-word
-  // entry, start_make's half of the start -- rd.x, rd.y, d, rng before the time draw -- and the ring's first id once
-  // per wave (an entry's id is that + its index); the lanes that take an entry finish it with start_take.
+  // entry, start_make's half of the start -- rd.x, rd.y, u, v, rng before the time draw -- with the first segment's
+  // closest hit where the tile's list decides it (start_decide), and the ring's first id once per wave (an entry's id
+  // is that + its index); the lanes that take an entry finish it with start_take.
   // (the other LDS-node and the mesh kernels have no LDS left for a ring at their occupancy)
   // Its head and first id follow the wave's entries (RS words per wave), so one address serves all three.
   constexpr uint32_t RW = K.ring_words(), RS = RW * 64u + (K.ldsn_ring() ? 2u : 0u);
@@ -331,6 +378,8 @@ __global__ __launch_bounds__(K.blk) __attribute__((amdgpu_waves_per_eu(K.occ, 8)
   if (K.sring() && lane == 0) ring_head[0] = 64u;
   bool exhausted = false;                // wave-uniform
   bool has = false;
+  // K.ldsn_ring(): what the lane's ring entry knew of its path's first segment (start_decide), until that segment starts
+  int32_t start_win = START_WALK;
   TraceState ts;
   ts.on = false;
   PathState st;
@@ -365,9 +414,10 @@ __global__ __launch_bounds__(K.blk) __attribute__((amdgpu_waves_per_eu(K.occ, 8)
           if constexpr (K.ldsn_ring()) {  // the 7-word entry: start_take finishes it
             const uint32_t lo = ring[5 * 64 + e], hi = ring[6 * 64 + e];
             const float rdx = __uint_as_float(ring[e]), rdy = __uint_as_float(ring[64 + e]);
-            st.ray.d = mk(__uint_as_float(ring[2 * 64 + e]), __uint_as_float(ring[3 * 64 + e]),
-                          __uint_as_float(ring[4 * 64 + e]));
-            start_take<true, K.alignbit_draws()>(SA, rdx, rdy, ((uint64_t)hi << 32) | lo, ring_base[0] + e, st);
+            start_take<true, K.alignbit_draws()>(SA, rdx, rdy, __uint_as_float(ring[2 * 64 + e]),
+                                                 __uint_as_float(ring[3 * 64 + e]), ((uint64_t)hi << 32) | lo,
+                                                 ring_base[0] + e, st);
+            start_win = (int32_t)ring[4 * 64 + e];
             has = (lo | hi) != 0u;
           } else {
             const uint32_t lo = ring[7 * 64 + e], hi = ring[8 * 64 + e];
@@ -403,11 +453,12 @@ __global__ __launch_bounds__(K.blk) __attribute__((amdgpu_waves_per_eu(K.occ, 8)
             if constexpr (K.ldsn_ring()) {
               StartMade m;
               const bool ok = start_make<K.start_args_in_lds(), K.alignbit_draws()>(SA, id, m);
+              const int32_t win = start_decide<COUNT, K.feat, K.alignbit_draws()>(S, SA, a.tile_lists, m, cnt);
               ring[lane] = __float_as_uint(m.rdx);
               ring[64 + lane] = __float_as_uint(m.rdy);
-              ring[2 * 64 + lane] = __float_as_uint(m.d.x);
-              ring[3 * 64 + lane] = __float_as_uint(m.d.y);
-              ring[4 * 64 + lane] = __float_as_uint(m.d.z);
+              ring[2 * 64 + lane] = __float_as_uint(m.u);
+              ring[3 * 64 + lane] = __float_as_uint(m.v);
+              ring[4 * 64 + lane] = (uint32_t)win;
               ring[5 * 64 + lane] = ok ? (uint32_t)m.rng : 0u;
               ring[6 * 64 + lane] = ok ? (uint32_t)(m.rng >> 32) : 0u;
               if (lane == 0) ring_base[0] = (uint32_t)pool_next;
@@ -499,13 +550,24 @@ __global__ __launch_bounds__(K.blk) __attribute__((amdgpu_waves_per_eu(K.occ, 8)
     nrays += (unsigned long long)__popcll(__ballot(has && !ts.on));
     if (!has) continue;
     // ---- one segment: closest hit (resumable) + shading (lib.rs:97-117)
+    bool decided = false;  // K.ldsn_ring(): the segment starting now has its hit from the ring (no walk)
     if (!ts.on) {
-      trace_begin<COUNT, K.feat, K.stack, K.blk, K.codes16_stack(), K.far_lds_nodes()>(S, st.ray, ts, cnt, st.rng, stk16,
-                                                                                       stk, a.err, nodes_lds);
+      if constexpr (K.ldsn_ring()) {
+        decided = start_win != START_WALK;
+        trace_begin<COUNT, K.feat, K.stack, K.blk, K.codes16_stack(), K.far_lds_nodes(), true>(
+            S, st.ray, ts, cnt, st.rng, stk16, stk, a.err, nodes_lds, start_win);
+        start_win = START_WALK;
+      } else {
+        trace_begin<COUNT, K.feat, K.stack, K.blk, K.codes16_stack(), K.far_lds_nodes()>(S, st.ray, ts, cnt, st.rng, stk16,
+                                                                                         stk, a.err, nodes_lds);
+      }
     }
     if (!(K.feat & F_LIST)) {
       const uint32_t act = (uint32_t)__popcll(__ballot(1));
-      const uint32_t quota = (act * a.quota16 + 15u) >> 4;
+      // lanes whose segment is decided are done on entry: they stay out of the quota's base, which is a share of the
+      // lanes that walk
+      const uint32_t ndec = K.ldsn_ring() ? (uint32_t)__popcll(__ballot(decided)) : 0u;
+      const uint32_t quota = (((act - ndec) * a.quota16 + 15u) >> 4) + ndec;
       const uint32_t leaf_thr = (act * a.leaf16 + 15u) >> 4;
       trace_run<COUNT, K.stack, K.spill, K.feat, K.blk, K.ncap, K.half, K.s16>(S, st.ray, ts, stk, spill, a.spill_lanes, cnt,
                                                                               quota, leaf_thr, st.rng, a.err, ph + 4, nodes_lds, stk16);

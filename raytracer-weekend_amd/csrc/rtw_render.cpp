@@ -62,6 +62,13 @@ int upload(Scene& s, int device) {
       HIPCHK(hipMemcpy(c.mshade.p, f.mshade.data(), f.mshade.size() * sizeof(DevShade), hipMemcpyHostToDevice),
              "hipMemcpy(material shading records)");
     }
+    // the BVH primitives' padded boxes (the per-tile lists' builder): a buffer of their own, likewise
+    if (!f.pboxes.empty()) {
+      if (int e = grow(c.pboxes, f.pboxes.size() * sizeof(float))) return e;
+      HIPCHK(hipMemcpy(c.pboxes.p, f.pboxes.data(), f.pboxes.size() * sizeof(float), hipMemcpyHostToDevice),
+             "hipMemcpy(primitive boxes)");
+    }
+    HIPCHK(hipMalloc((void**)&c.lists_count, 64), "hipMalloc(tile-list counter)");
     uint8_t* base = (uint8_t*)c.block;
     c.scene.nodes = (const DevNode4*)(base + o_nodes);
     c.scene.hnodes = f.nodes4h.empty() ? nullptr : (const DevNode4h*)(base + o_hnodes);
@@ -111,8 +118,9 @@ void release(Scene& s) {
     if (c.block) hipFree(c.block);
     if (c.counters) hipFree(c.counters);
     if (c.err_host) hipHostFree(c.err_host);
+    if (c.lists_count) hipFree(c.lists_count);
     for (DevBuf* b : {&c.sbuf, &c.spill, &c.image, &c.tiles, &c.packed, &c.gathered, &c.gather_ids, &c.qrays, &c.qhits,
-                       &c.mshade, &c.qscatter, &c.qsamples})
+                       &c.mshade, &c.qscatter, &c.qsamples, &c.pboxes, &c.tile_lists})
       free_buf(*b);
     for (hipEvent_t e : {c.ev[0], c.ev[1], c.gev[0], c.gev[1]})
       if (e) hipEventDestroy(e);

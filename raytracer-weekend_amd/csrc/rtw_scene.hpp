@@ -69,6 +69,7 @@ struct Flat {
   std::vector<DevShade> shade;  // per prim: material + common texture values (rtw_device.hpp)
   std::vector<DevShade> mshade;  // the same record per material: shade[k] = mshade[prims[k].mat] (rtw_scatter_rays)
   std::vector<uint32_t> always;
+  std::vector<float> pboxes;  // per BVH prim (prims[0 .. n_bvh)): its padded, swept box, 8 floats (lo, 0, hi, 0)
   std::vector<DevTriShade> tshade;
   std::vector<DevInst> insts;
   std::vector<DevMat> mats;
@@ -126,6 +127,19 @@ struct DeviceCopy {
   DevBuf mshade;                           // Flat::mshade (uploaded with the scene; scatter_kernel's material table)
   DevBuf qscatter;                         // rtw_scatter_rays' staging: one chunk of rtw_scatter records
   DevBuf qsamples;                         // rtw_sample_rays' staging: one chunk of rtw_sample records
+  DevBuf pboxes;                           // Flat::pboxes (uploaded with the scene; tile_list_kernel's box table)
+  DevBuf tile_lists;                       // one 32-B record per 8x8 tile of the last frame (tile_list_kernel)
+  // the last render on this copy: 1 = its camera rays were resolved from the tile lists; tiles whose list overflowed
+  uint32_t lists_used = 0, lists_overflow = 0;
+  uint32_t* lists_count = nullptr;         // device word: the list builder's overflow count
+  // what c.tile_lists holds: the (camera, size, cap) its records were built for and the stream that built them (a
+  // render with the same ones on the same stream reuses them: enqueue_render)
+  struct ListsKey {
+    rtw_camera cam;
+    uint32_t w = 0, h = 0, cap = 0;
+    hipStream_t stream = nullptr;
+    bool valid = false;
+  } lists_key;
   hipEvent_t ev[2] = {nullptr, nullptr};   // pair timing rtw_render / multi calls (copy_events)
   hipStream_t stream = nullptr;            // rtw_render_multi's stream on this device
   hipEvent_t gev[2] = {nullptr, nullptr};  // pair around rtw_render_multi's gather (device 0)
@@ -231,6 +245,8 @@ float recip_rn(float b);  // RN(1 / b) for an integer-valued b in [1, 2^24) (rtw
 // field 0-7 (stack, spill, occ, feat, blk, ncap, half, s16) of the path-kernel configuration the current
 // environment selects for the committed scene (rtw_scene_info 16-23); host only, no device needed
 int64_t selected_kernel_info(const Scene& s, int field);
+// rtw_scene_info 24 (field 0), 25 (field 1): the tile lists of the last render on the first device copy
+int64_t last_render_lists(Scene& s, int field);
 // enqueue one render (path kernel passes + in-order reductions) on `stream` of c.device, which must be current;
 // ev0 / ev1 (or NULL) are recorded around it
 int enqueue_render(Scene& s, DeviceCopy& c, const Frame& f, const TileSet& tiles, float* d_out, hipStream_t stream,

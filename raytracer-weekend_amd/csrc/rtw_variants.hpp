@@ -38,6 +38,7 @@ struct Knob {
 struct Knobs {
   Knob stack_lds, half_nodes, generic, list_all, list_occ, occ, ldsn_waves, lds_nodes, ldsn_blk, mesh_s16;  // selection
   Knob batch, quota16, leaf16, regen_min, pass_log2;                                                        // launch
+  Knob tile_lists, tile_list_cap;  // the per-tile lists of camera rays (0 = off; 1..15 candidates per tile)
   bool verbose = false;
 };
 
