@@ -237,6 +237,54 @@ int rtw_render_device_strided(rtw_scene* s, int device, const rtw_camera* cam, c
                               uint32_t w, uint32_t h, uint32_t spp, uint32_t max_depth, uint64_t seed,
                               uint32_t first_tile, uint32_t tile_stride, uint32_t n_tiles, float* d_out,
                               void* stream, uint32_t flags, rtw_stats* stats);
+
+/* ---- progressive renders: more samples onto a frame that exists (preview at 1, 2, 4 ... spp, resuming, spreading a
+ *      frame over time), with the per-pixel sum of squares for a noise estimate.  The path generator is keyed by
+ *      (seed, j, i, sample) and a frame is the in-order f32 sum over its samples, so samples [a, b) added onto the sums
+ *      of [0, a) are rtw_render's frame of b samples bit for bit, with the same number of rays, however [0, b) is cut. */
+/* Samples [sample_first, sample_first + n_samples) of every pixel of the tile set, ADDED in sample order onto what
+ * d_sum (and d_sq, may be NULL) hold: zeroed buffers = a fresh frame.  d_sq, a second device buffer of d_sum's layout,
+ * receives per channel m = m + (x * x) in the same order (two f32 roundings).  Tile arguments, layouts, stream, flags
+ * and stats as rtw_render_device; pixels outside the image, tiles not named and ids beyond the last tile are left
+ * untouched in both buffers.  Checks in the render calls' order: a NULL argument (RTW_EINVAL), an uncommitted scene
+ * (RTW_ESTATE), an image under 2x2, then sample_first + n_samples > 2^31 (both RTW_EINVAL), then the device copy
+ * (RTW_ENODEV).  n_samples = 0 or max_depth = 0 is RTW_OK and leaves both buffers untouched (every such sample is
+ * black, and adding +0 would only turn a -0 into +0).  The range runs as the aligned power-of-two blocks of
+ * rtw_sample_blocks, each an ordinary pass of the scene's path kernel: stats->rays sums them.  The call shares the
+ * (scene, device) pair's path queue, sample buffer (grown for the largest block) and spill area: it must be serialised
+ * with the pair's renders and queries on one stream, as rtw_render_device. */
+int rtw_render_samples_device(rtw_scene* s, int device, const rtw_camera* cam, const float background[3],
+                              uint32_t w, uint32_t h, uint32_t sample_first, uint32_t n_samples,
+                              uint32_t max_depth, uint64_t seed, const uint32_t* d_tile_ids, uint32_t n_tiles,
+                              float* d_sum, float* d_sq, void* stream, uint32_t flags, rtw_stats* stats);
+/* host only: the aligned power-of-two blocks the call above runs, in order (block k = [first[k], first[k] + 2^log2[k]),
+ * first[k] a multiple of its size): at each position the largest such block that fits what is left, hence at most 62.
+ * *n_blocks = their number; RTW_EINVAL if cap is smaller (nothing written) or the range goes beyond 2^31. */
+int rtw_sample_blocks(uint32_t sample_first, uint32_t n_samples, uint32_t* first, uint32_t* log2, uint32_t cap,
+                      uint32_t* n_blocks);
+/* Receives the frame after a step: host copies (they belong to the call) of the sums and sums of squares in
+ * rtw_render's layout, and the samples per pixel they hold.  A non-zero return stops the render (returned as is). */
+typedef int (*rtw_frame_sink)(const float* rgb_sum, const float* rgb_sq_sum, uint32_t w, uint32_t h,
+                              uint32_t samples_done, void* user);
+/* Blocking, first device copy: a frame of spp samples (<= 2^31) in growing steps, the sink called after each with host
+ * copies of both sums; a non-zero return stops the render and is returned as is.  step = 0: the steps end at 1, 2, 4,
+ * 8, ... samples and then at spp; step > 0: doubling while the doubled count is within step, then step samples at a
+ * time (a power-of-two step keeps every chunk but the last one block of rtw_sample_blocks).  The last call's rgb_sum
+ * is rtw_render's image.  The device sums live in buffers the device copy keeps (grown once).  stats: totals over the
+ * whole call.  spp = 0 calls the sink never.  Checks as above, `sink` among the NULL arguments.  (`sink` is an
+ * rtw_frame_sink, its type written out: the header parser of tests/test_integration_abi.py lists the prototypes whose
+ * parameter types it knows by name, and tests/test_render_samples_abi.py holds this one against the typedef.) */
+int rtw_render_progressive(rtw_scene* s, const rtw_camera* cam, const float background[3], uint32_t w, uint32_t h,
+                           uint32_t spp, uint32_t max_depth, uint64_t seed, uint32_t step,
+                           int (*sink)(const float* rgb_sum, const float* rgb_sq_sum, uint32_t w, uint32_t h,
+                                       uint32_t samples_done, void* user),
+                           void* user, rtw_stats* stats);
+/* rtw_tonemap (below) from a DEVICE sum image to a DEVICE RGB8 image on `stream`, byte for byte: a preview then costs
+ * 3 B per pixel to copy.  Only enqueues.  device < 0: the current device.  RTW_EINVAL: a NULL buffer with n_pixels > 0,
+ * spp = 0. */
+int rtw_tonemap_device(int device, const float* d_rgb_sum, uint32_t n_pixels, uint32_t spp, uint8_t* d_rgb8,
+                       void* stream);
+
 /* ---- closest-hit ray queries: Hittable::hit(&ray, t_min, t_max) -> Option<HitRecord> on the world list
  *      (hittable/mod.rs:22-69) for rays the caller chooses.  A query is world.hit(ray, 0.001, +inf), the interval of
  *      lib.rs:102 and the only one the render's culling is proven for: t_min and t_max are not parameters.  The winner

@@ -111,6 +111,9 @@ HIT_DTYPE = np.dtype([("p", np.float32, 3), ("normal", np.float32, 3), ("t", np.
 MSG_IMAGE_START, MSG_PIXEL, MSG_IMAGE_END = 0, 1, 2
 PIXEL_SINK = C.CFUNCTYPE(C.c_int, C.POINTER(rtw_pixel), C.c_uint32, C.c_void_p)
 PIXEL_DTYPE = np.dtype([("row", np.uint32), ("column", np.uint32), ("color", np.float32, 3)])
+# rtw_frame_sink: (rgb_sum, rgb_sq_sum, w, h, samples_done, user) -> int
+FRAME_SINK = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_uint32,
+                         C.c_void_p)
 
 _F = C.POINTER(C.c_float)
 _U32 = C.POINTER(C.c_uint32)
@@ -155,6 +158,14 @@ _SIGS = {
     "rtw_render_device_strided": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(rtw_camera), _F, C.c_uint32,
                                             C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32,
                                             C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(rtw_stats)]),
+    "rtw_render_samples_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(rtw_camera), _F, C.c_uint32, C.c_uint32,
+                                            C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, _U32, C.c_uint32,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(rtw_stats)]),
+    "rtw_sample_blocks": (C.c_int, [C.c_uint32, C.c_uint32, _U32, _U32, C.c_uint32, _U32]),
+    "rtw_render_progressive": (C.c_int, [C.c_void_p, C.POINTER(rtw_camera), _F, C.c_uint32, C.c_uint32, C.c_uint32,
+                                         C.c_uint32, C.c_uint64, C.c_uint32, FRAME_SINK, C.c_void_p,
+                                         C.POINTER(rtw_stats)]),
+    "rtw_tonemap_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rtw_hit_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(rtw_ray), C.POINTER(rtw_hit),
                                C.POINTER(rtw_stats)]),
     "rtw_hit_rays_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -681,6 +692,65 @@ class Raytracer:
             self.seed, first_tile, tile_stride, n_tiles, C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr), flags,
             C.byref(st) if want_stats else None))
         return st.as_dict() if want_stats else None
+
+
+    def render_samples_device(self, d_sum_ptr: int, d_sq_ptr: int = 0, sample_first: int = 0, n_samples=None,
+                              device: int = 0, d_tiles_ptr: int = 0, n_tiles: int = 0, stream_ptr: int = 0,
+                              flags: int = 0, want_stats: bool = False):
+        """Enqueue samples [sample_first, sample_first + n_samples) (n_samples = None: up to the frame's spp), ADDED in
+        sample order onto the device sums at d_sum_ptr and, unless 0, the sums of squares at d_sq_ptr (zeroed buffers =
+        a fresh frame); tiles and layouts as render_device.  Chunks that cover [0, spp) give render()'s frame bit for
+        bit."""
+        n = max(self.spp - sample_first, 0) if n_samples is None else n_samples
+        st = rtw_stats()
+        _check(lib().rtw_render_samples_device(
+            self.scene._p, device, C.byref(self.cam.c), _fp(self.bg), self.w, self.h, sample_first, n, self.max_depth,
+            self.seed, C.cast(C.c_void_p(d_tiles_ptr), _U32) if d_tiles_ptr else None, n_tiles,
+            C.c_void_p(d_sum_ptr), C.c_void_p(d_sq_ptr) if d_sq_ptr else None, C.c_void_p(stream_ptr), flags,
+            C.byref(st) if want_stats else None))
+        return st.as_dict() if want_stats else None
+
+    def render_progressive(self, on_frame, step: int = 0):
+        """The frame in growing steps (rtw_render_progressive: they end at 1, 2, 4, ... samples while the doubled count
+        is within `step`, then every `step` samples; 0 = doubling, then spp): on_frame(sums[h, w, 3], sums of
+        squares[h, w, 3], samples_done) after each, on copies it may keep.  A return value that is true as an int
+        stops the render.  -> (that value, or 0 after the last step; stats: totals over the call)."""
+        err = []
+        shape = (self.h, self.w, 3)
+
+        def sink(p_sum, p_sq, _w, _h, done, _user):
+            try:
+                a = np.ctypeslib.as_array(p_sum, shape=shape).copy()
+                b = np.ctypeslib.as_array(p_sq, shape=shape).copy()
+                return int(on_frame(a, b, int(done)) or 0)
+            except Exception as e:  # stop the render, re-raise below
+                err.append(e)
+                return RTW_ESTATE
+
+        cb = FRAME_SINK(sink)
+        st = rtw_stats()
+        rc = lib().rtw_render_progressive(self.scene._p, C.byref(self.cam.c), _fp(self.bg), self.w, self.h, self.spp,
+                                          self.max_depth, self.seed, step, cb, None, C.byref(st))
+        if err:
+            raise err[0]
+        if rc < 0:
+            _check(rc)
+        return rc, st.as_dict()
+
+
+def sample_blocks(sample_first: int, n_samples: int) -> list:
+    """rtw_sample_blocks -> [(first, log2 of the size)]: the aligned power-of-two blocks, in order, that
+    render_samples_device runs the range as (host only)."""
+    first, log2 = np.zeros(62, np.uint32), np.zeros(62, np.uint32)
+    n = C.c_uint32()
+    _check(lib().rtw_sample_blocks(sample_first, n_samples, _up(first), _up(log2), 62, C.byref(n)))
+    return [(int(first[k]), int(log2[k])) for k in range(n.value)]
+
+
+def tonemap_device(d_sum_ptr: int, n_pixels: int, spp: int, d_rgb8_ptr: int, device: int = -1, stream_ptr: int = 0):
+    """tonemap() over device arrays (n_pixels x 3 float sums -> n_pixels x 3 bytes), enqueued on a stream."""
+    _check(lib().rtw_tonemap_device(device, C.c_void_p(d_sum_ptr), n_pixels, spp, C.c_void_p(d_rgb8_ptr),
+                                    C.c_void_p(stream_ptr)))
 
 
 def make_rays(origins, directions, times=None, streams=None) -> np.ndarray:

@@ -16,10 +16,13 @@
 //   cam.get_ray(u, v, rng) per path of a frame          world.camera_rays(cam, w, h, spp, seed) -> std::vector<Ray>  camera.rs:66-74
 //   rec.material.scatter(&ray, &rec, rng) / emitted()   world.scatter_rays(rays, hits, background) -> {rays, Scatter}  material.rs:23-26
 //   raytracer.sample_ray(&ray, rng, depth) -> Color      world.sample_rays(rays, background, max_depth) -> std::vector<Sample>  lib.rs:97-117
+//   (no counterpart: the frame in growing steps)        Raytracer(..).render_progressive(on_frame, step); sample_blocks; tonemap_device
 // Errors (the reference panics) throw rtw::Error with rtw_last_error()'s message.
 #pragma once
 #include <stdexcept>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/rtw.h"
@@ -254,6 +257,29 @@ class Raytracer {
       }
     return px;
   }
+  // The frame in growing steps (rtw_render_progressive): on_frame(sums, sums of squares, samples done) -> int after
+  // each, flat RGB in render_sums' layout; a non-zero return stops the render and comes back as the result.
+  template <class F> int render_progressive(F&& on_frame, uint32_t step = 0, rtw_stats* st = nullptr) const {
+    const float bg[3] = {bg_.x, bg_.y, bg_.z};
+    auto* fn = &on_frame;
+    using Fn = typename std::remove_reference<F>::type;
+    const rtw_frame_sink sink = [](const float* sum, const float* sq, uint32_t, uint32_t, uint32_t done, void* user) {
+      return (int)(*static_cast<Fn*>(user))(sum, sq, done);
+    };
+    const int rc = rtw_render_progressive(world_.raw(), &cam_.c, bg, w_, h_, spp_, depth_, seed_, step, sink,
+                                          const_cast<void*>(static_cast<const void*>(fn)), st);
+    if (rc < 0) check(rc);
+    return rc;
+  }
+  // Samples [first, first + n) of the tile set added onto the device sums d_sum and d_sq (or nullptr)
+  // (rtw_render_samples_device; the constructor's spp is not used); d_tile_ids = nullptr: the whole image
+  void render_samples_device(int device, uint32_t first, uint32_t n, float* d_sum, float* d_sq,
+                             const uint32_t* d_tile_ids = nullptr, uint32_t n_tiles = 0, void* stream = nullptr,
+                             uint32_t flags = 0, rtw_stats* st = nullptr) const {
+    const float bg[3] = {bg_.x, bg_.y, bg_.z};
+    check(rtw_render_samples_device(world_.raw(), device, &cam_.c, bg, w_, h_, first, n, depth_, seed_, d_tile_ids,
+                                    n_tiles, d_sum, d_sq, stream, flags, st));
+  }
 
  private:
   World& world_;
@@ -263,5 +289,19 @@ class Raytracer {
   uint64_t seed_;
   uint32_t depth_;
 };
+
+// the aligned power-of-two blocks (first, log2 of the size) samples [first, first + n) run as (rtw_sample_blocks)
+inline std::vector<std::pair<uint32_t, uint32_t>> sample_blocks(uint32_t first, uint32_t n) {
+  uint32_t f[62], l[62], nb = 0;
+  check(rtw_sample_blocks(first, n, f, l, 62, &nb));
+  std::vector<std::pair<uint32_t, uint32_t>> out(nb);
+  for (uint32_t k = 0; k < nb; ++k) out[k] = {f[k], l[k]};
+  return out;
+}
+// rtw_tonemap over device arrays, enqueued on `stream` (rtw_tonemap_device)
+inline void tonemap_device(const float* d_rgb_sum, uint32_t n_pixels, uint32_t spp, uint8_t* d_rgb8, int device = -1,
+                           void* stream = nullptr) {
+  check(rtw_tonemap_device(device, d_rgb_sum, n_pixels, spp, d_rgb8, stream));
+}
 
 }  // namespace rtw

@@ -1,9 +1,11 @@
 // rtw_console.cpp — the build's console_app (console_app/src/main.rs:15-96) on the GPU core.
 //
 //   rtw_console <scene> [-w|--width 400] [-a|--aspect-ratio 1.7777778] [-s|--samples-per-pixel 100]
-//               [--seed 0] [--models models] [--out render]
+//               [--seed 0] [--models models] [--out render] [--progressive STEP]
 // Same Opts and defaults (main.rs:15-26), height = round(width / aspect) (:33), camera
 // aspect = width / height as f32 (:38-41), tonemap (:68-90), PNG to render/image_0000.png (:92-94).
+// --progressive (no counterpart in console_app) renders each frame through rtw_render_progressive: the PNG is rewritten
+// after every step, and its last version is the one-shot frame's file byte for byte.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -53,9 +55,31 @@ static bool write_png(const char* path, const uint8_t* rgb, uint32_t w, uint32_t
   return fclose(f) == 0;
 }
 
+// The frame's mean relative standard error from the two sums, n samples in (--help states the definition)
+static double mean_rel_stderr(const float* sum, const float* sq, size_t n_pixels, uint32_t n) {
+  static const double wgt[3] = {0.2126, 0.7152, 0.0722};
+  double tot = 0.0;
+  size_t lit = 0;
+  for (size_t p = 0; p < n_pixels; ++p) {
+    double mean = 0.0, se = 0.0;
+    for (int c = 0; c < 3; ++c) {
+      const double m = (double)sum[p * 3 + c] / n;
+      const double v = fmax(0.0, (double)sq[p * 3 + c] / n - m * m) * n / (n - 1.0);
+      mean += wgt[c] * m;
+      se += wgt[c] * sqrt(v / n);
+    }
+    if (mean != 0.0 && mean == mean && se == se) {
+      tot += se / fabs(mean);
+      ++lit;
+    }
+  }
+  return lit ? tot / (double)lit : 0.0;
+}
+
 int main(int argc, char** argv) {
   std::string scene, models = "models", out_dir = "render";
-  uint32_t width = 400, spp = 100;
+  uint32_t width = 400, spp = 100, step = 0;
+  bool progressive = false;
   double aspect = 1.7777778;
   uint64_t seed = 0;
   for (int k = 1; k < argc; ++k) {
@@ -70,11 +94,20 @@ int main(int argc, char** argv) {
     else if (a == "--seed") seed = strtoull(next("--seed"), nullptr, 0);
     else if (a == "--models") models = next("--models");
     else if (a == "--out") out_dir = next("--out");
+    else if (a == "--progressive") { progressive = true; step = (uint32_t)atoi(next("--progressive")); }
     else if (a == "-h" || a == "--help") {
       printf("usage: rtw_console <jumpy-balls|two-spheres|two-perlin-spheres|earth|simple-light|cornell-box|"
              "smokey-cornell-box|book2-final-scene|animated-book2-final-scene|simple-triangle|wavefront-cow-obj|"
              "wavefront-suspension-obj|textured-monument> [-w W] [-a ASPECT] [-s SPP] [--seed N] [--models DIR] "
-             "[--out DIR]\n");
+             "[--out DIR] [--progressive STEP]\n"
+             "  --progressive STEP  render each frame in growing steps (1, 2, 4, ... samples while the doubled count is\n"
+             "      within STEP, then STEP at a time; 0 = doubling to the end); after every step the frame's PNG is\n"
+             "      rewritten and the samples done and the mean relative standard error are printed.  That error, from\n"
+             "      the per-pixel sums S and sums of squares Q over n samples: per channel the mean m = S / n and the\n"
+             "      variance v = max(0, Q / n - m^2) n / (n - 1); the luminance Y = 0.2126 R + 0.7152 G + 0.0722 B has\n"
+             "      mean sum_c w_c m_c and standard error sum_c w_c sqrt(v_c / n) (the channels taken as fully\n"
+             "      correlated: an upper bound); a pixel's relative error is the second over the first, and the frame's\n"
+             "      is its average over the pixels whose mean luminance is not zero (n/a at n = 1).\n");
       return 0;
     } else if (scene.empty()) scene = a;
     else { fprintf(stderr, "unexpected argument '%s'\n", a.c_str()); return 2; }
@@ -93,13 +126,26 @@ int main(int argc, char** argv) {
     for (size_t frame = 0; frame < cams.size(); ++frame) {
       rtw::Raytracer rt(world, cams[frame], bg, width, height, spp, seed);
       rtw_stats st;
-      std::vector<float> sums = rt.render_sums(&st);
-      std::vector<uint8_t> img(sums.size());
-      rtw::check(rtw_tonemap(sums.data(), width * height, spp, img.data()));
       char name[32];
       snprintf(name, sizeof name, "/image_%04zu.png", frame);  // main.rs:92-94
       std::string path = out_dir + name;
-      if (!write_png(path.c_str(), img.data(), width, height)) { fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
+      std::vector<uint8_t> img((size_t)width * height * 3);
+      if (progressive) {
+        const int rc = rt.render_progressive([&](const float* sum, const float* sq, uint32_t done) {
+          if (rtw_tonemap(sum, width * height, done, img.data()) != RTW_OK) return 1;  // (nothing throws through C)
+          if (!write_png(path.c_str(), img.data(), width, height)) return 1;
+          if (done > 1) printf("  %u spp: mean relative standard error %.4f\n", done,
+                               mean_rel_stderr(sum, sq, (size_t)width * height, done));
+          else printf("  %u spp: mean relative standard error n/a\n", done);
+          fflush(stdout);
+          return 0;
+        }, step, &st);
+        if (rc) { fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
+      } else {
+        std::vector<float> sums = rt.render_sums(&st);
+        rtw::check(rtw_tonemap(sums.data(), width * height, spp, img.data()));
+        if (!write_png(path.c_str(), img.data(), width, height)) { fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
+      }
       printf("%s %ux%u %u spp: %.1f ms kernel, %llu rays, %.1f Mrays/s -> %s\n", scene.c_str(), width, height, spp,
              st.kernel_ms, (unsigned long long)st.rays, st.rays / (st.kernel_ms * 1e3), path.c_str());
     }

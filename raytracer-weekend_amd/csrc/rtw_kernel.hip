@@ -1,7 +1,8 @@
 // rtw_kernel.hip — what of the gfx950 path-tracing megakernel's host side needs the device compiler: the kernels
 // that are no templates (reduce_kernel, unpack_tiles_kernel, tile_list_kernel with its diagnostic calls, the libm and
 // reciprocal diagnostics, with the two calls that launch the latter), the tuning knobs, pick_kernel (which path-kernel variant a scene runs) and the launches
-// (enqueue_render, enqueue_hit_rays, enqueue_sample_rays, enqueue_scatter_rays, enqueue_camera_rays, enqueue_unpack),
+// (enqueue_render, enqueue_render_samples, enqueue_tonemap, enqueue_hit_rays, enqueue_sample_rays, enqueue_scatter_rays,
+// enqueue_camera_rays, enqueue_unpack),
 // which share one cache of resident grids (resident_blocks), the walk's tuning (tune_walk) and the one-record-per-lane
 // queries' launch (launch_query).  The
 // scene's device copies, statistics and the render entry points are plain HIP runtime code in rtw_render.cpp, the
@@ -43,6 +44,9 @@
 // Scatter and camera-ray queries (rtw_scatter_rays*, rtw_camera_rays*): scatter_kernel and camera_rays_kernel
 // (rtw_shade_kernel.hpp) run the materials' body and restate start_path over record arrays; one instantiation each, this
 // unit only.
+// Progressive renders (rtw_render_samples_device, rtw_render_progressive): a range of samples runs as aligned
+// power-of-two blocks, each an ordinary round of passes whose key carries the block's base (frame_args), reduced by
+// accumulate_kernel (rtw_film_kernel.hpp) onto the sums the frame holds; tonemap_kernel beside it (rtw_tonemap_device).
 // Variants: path_kernel<COUNT, KernelCfg K> -- one plain aggregate (stack rows, spill, waves / SIMD, feature set,
 // workgroup size, LDS node table, half nodes, 16-bit stack) is the template argument, defines every property derived
 // from it, and travels with the kernel to the host (Variant, rtw_variants.hpp), which sizes the launch from it.
@@ -63,6 +67,7 @@
 #include "rtw_scene.hpp"
 #include "rtw_variants.hpp"
 #include "rtw_shade_kernel.hpp"
+#include "rtw_film_kernel.hpp"
 #include "rtw_tile_beam.h"
 
 namespace rtw {
@@ -420,7 +425,9 @@ static RenderArgs frame_args(const DeviceCopy& c, const Frame& f, const TileSet&
   uint64_t z = f.seed + 0x9E3779B97F4A7C15ull;
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  a.seed_hash = z ^ (z >> 31);
+  // the path key is seed_hash ^ (j << 48 | i << 32 | s) with s < spp (start_path): a block's base, a multiple of its
+  // power-of-two spp, joins s here (base ^ s == base + s)
+  a.seed_hash = (z ^ (z >> 31)) ^ (uint64_t)f.sample_base;
   a.out = d_out;
   a.counters = c.counters;
   a.queue = dispensers(c);
@@ -497,14 +504,27 @@ static uint32_t pass_batch(uint32_t batch0, uint64_t n_paths, uint64_t waves) {
   return batch;
 }
 
+// The ordered sample buffer's bytes for passes of `spp` samples over n_slots tiles: the largest pass's paths
+static size_t sample_buffer_bytes(const Knobs& kn, uint32_t n_slots, uint32_t spp) {
+  const uint64_t per_slot = 64ull * spp;
+  const uint64_t slots_per_pass = std::max<uint64_t>(1, max_pass_paths(kn) / per_slot);
+  return (size_t)(std::min<uint64_t>(n_slots, slots_per_pass) * per_slot * 3 * sizeof(float));
+}
+
+// What a pass's in-order reduction does with the sums: nullptr = reduce_kernel starts them (rtw_render*); a Film =
+// accumulate_kernel continues the ones at RenderArgs::out, and the sums of squares at sq when there is one
+struct Film {
+  float* sq;
+};
+
 // enqueue_render, part 3: the pass loop over n_slots tiles, each pass one persistent launch of the scene's variant and
 // its in-order reduction
 static int run_passes(Scene& sc, DeviceCopy& c, RenderArgs& a, const Knobs& kn, uint32_t n_slots, bool count,
-                      hipStream_t stream) {
+                      hipStream_t stream, const Film* film = nullptr) {
   const uint64_t per_slot = 64ull * a.spp;
   const uint32_t slots_per_pass = (uint32_t)std::max<uint64_t>(1, max_pass_paths(kn) / per_slot);
-  const uint64_t need = std::min<uint64_t>(n_slots, slots_per_pass) * per_slot;
-  if (int e = grow(c.sbuf, need * 3 * sizeof(float))) return e;  // the ordered sample buffer (first render only)
+  // the ordered sample buffer (first render only)
+  if (int e = grow(c.sbuf, sample_buffer_bytes(kn, n_slots, a.spp))) return e;
   a.sbuf = static_cast<float*>(c.sbuf.p);
   const Variant var = path_kernel_variant(sc.flat, kn);
   const KernelCfg& k = var.cfg;
@@ -541,8 +561,14 @@ static int run_passes(Scene& sc, DeviceCopy& c, RenderArgs& a, const Knobs& kn, 
     HIPCHK(hipEventRecord(ke[1], stream), "hipEventRecord");
     c.kev_head = (c.kev_head + 1) % 64u;
     c.kev_count = std::min(c.kev_count + 1u, 64u);
-    hipLaunchKernelGGL(dev::reduce_kernel, dim3((ns * 64u + 255u) / 256u), dim3(256), 0, stream, a, ns);
-    HIPCHK(hipGetLastError(), "reduce_kernel launch");
+    if (film) {
+      hipLaunchKernelGGL(dev::accumulate_kernel, dim3((ns * 64u + dev::FILM_BLOCK - 1u) / dev::FILM_BLOCK),
+                         dim3(dev::FILM_BLOCK), 0, stream, a, ns, film->sq, film->sq ? 1u : 0u);
+      HIPCHK(hipGetLastError(), "accumulate_kernel launch");
+    } else {
+      hipLaunchKernelGGL(dev::reduce_kernel, dim3((ns * 64u + 255u) / 256u), dim3(256), 0, stream, a, ns);
+      HIPCHK(hipGetLastError(), "reduce_kernel launch");
+    }
   }
   return RTW_OK;
 }
@@ -609,6 +635,35 @@ static bool tile_lists_on(const Scene& sc, const DeviceCopy& c, const rtw_camera
          lens_is_near(sc.flat, cam);
 }
 
+// The frame's tile lists, before its passes (records by global tile id: every tile subset, pass and block of samples
+// reads the same table): sets c.lists_used and *lists (NULL when the render does not use them)
+static int frame_tile_lists(Scene& sc, DeviceCopy& c, const Frame& f, hipStream_t stream, const uint32_t** lists) {
+  uint32_t cap = 0;
+  *lists = nullptr;
+  c.lists_used = tile_lists_on(sc, c, *f.cam, &cap) ? 1u : 0u;
+  if (!c.lists_used) return RTW_OK;
+  // (the buffer is grown once, like the sample buffer)
+  // The build measured 0.2 ms at 1080p (profiles/r08/experiments), above the 0.1 ms a rebuild per call was
+  // allowed: the records are kept for the (camera, size, cap) they were built for, compared field by field, and a
+  // render on the same stream with the same ones reuses them (an animation's frames rebuild, a frame's tile
+  // subsets, passes and repeats do not)
+  DeviceCopy::ListsKey& key = c.lists_key;
+  const bool same = key.valid && key.w == f.w && key.h == f.h && key.cap == cap && key.stream == stream &&
+                    memcmp(&key.cam, f.cam, sizeof key.cam) == 0;
+  if (!same) {
+    key.valid = false;
+    if (int e = grow(c.tile_lists, (size_t)f.tiles() * TILE_LIST_WORDS * sizeof(uint32_t))) return e;
+    if (int e = enqueue_tile_lists(sc, c, *f.cam, f.w, f.h, cap, static_cast<uint32_t*>(c.tile_lists.p),
+                                   c.lists_count, stream))
+      return e;
+    key.cam = *f.cam;
+    key.w = f.w; key.h = f.h; key.cap = cap; key.stream = stream;
+    key.valid = true;
+  }
+  *lists = static_cast<const uint32_t*>(c.tile_lists.p);
+  return RTW_OK;
+}
+
 int enqueue_render(Scene& sc, DeviceCopy& c, const Frame& f, const TileSet& ts, float* d_out, hipStream_t stream,
                    uint32_t flags, hipEvent_t ev0, hipEvent_t ev1) {
   // an earlier render on this device (one the caller did not wait on) tripped the guard: report it now
@@ -624,32 +679,67 @@ int enqueue_render(Scene& sc, DeviceCopy& c, const Frame& f, const TileSet& ts, 
     size_t n = a.packed_out ? (size_t)ts.n * 64 * 3 : (size_t)f.w * f.h * 3;
     HIPCHK(hipMemsetAsync(d_out, 0, n * sizeof(float), stream), "hipMemsetAsync(out)");
   } else if (ts.n) {
-    // the frame's tile lists first (records by global tile id: every tile subset and pass reads the same table)
-    uint32_t cap = 0;
-    c.lists_used = tile_lists_on(sc, c, *f.cam, &cap) ? 1u : 0u;
-    if (c.lists_used) {  // (the buffer is grown once, like the sample buffer)
-      // The build measured 0.2 ms at 1080p (profiles/r08/experiments), above the 0.1 ms a rebuild per call was
-      // allowed: the records are kept for the (camera, size, cap) they were built for, compared field by field, and a
-      // render on the same stream with the same ones reuses them (an animation's frames rebuild, a frame's tile
-      // subsets, passes and repeats do not)
-      DeviceCopy::ListsKey& key = c.lists_key;
-      const bool same = key.valid && key.w == f.w && key.h == f.h && key.cap == cap && key.stream == stream &&
-                        memcmp(&key.cam, f.cam, sizeof key.cam) == 0;
-      if (!same) {
-        key.valid = false;
-        if (int e = grow(c.tile_lists, (size_t)f.tiles() * TILE_LIST_WORDS * sizeof(uint32_t))) return e;
-        if (int e = enqueue_tile_lists(sc, c, *f.cam, f.w, f.h, cap, static_cast<uint32_t*>(c.tile_lists.p),
-                                       c.lists_count, stream))
-          return e;
-        key.cam = *f.cam;
-        key.w = f.w; key.h = f.h; key.cap = cap; key.stream = stream;
-        key.valid = true;
-      }
-      a.tile_lists = static_cast<const uint32_t*>(c.tile_lists.p);
-    }
+    if (int e = frame_tile_lists(sc, c, f, stream, &a.tile_lists)) return e;
     if (int e = run_passes(sc, c, a, kn, ts.n, flags & RTW_FLAG_COUNT_TRAVERSAL, stream)) return e;
   }
   if (ev1) HIPCHK(hipEventRecord(ev1, stream), "hipEventRecord");
+  return RTW_OK;
+}
+
+uint32_t sample_blocks(uint32_t first, uint32_t n, uint32_t* firsts, uint32_t* log2s) {
+  uint32_t nb = 0;
+  for (uint64_t p = first, end = (uint64_t)first + n; p < end; ++nb) {
+    uint32_t k = p ? (uint32_t)__builtin_ctzll(p) : 31u;  // the largest block that may start at p ...
+    while ((1ull << k) > end - p) --k;                    // ... and fits what is left
+    firsts[nb] = (uint32_t)p;
+    log2s[nb] = k;
+    p += 1ull << k;
+  }
+  return nb;
+}
+
+int enqueue_render_samples(Scene& sc, DeviceCopy& c, const Frame& f, uint32_t sample_first, const TileSet& ts,
+                           float* d_sum, float* d_sq, hipStream_t stream, uint32_t flags, hipEvent_t ev0,
+                           hipEvent_t ev1) {
+  if (int e = check_guard(c)) return e;
+  if (int e = check_image_max(f.w, f.h)) return e;
+  if (int e = check_shutter(*f.cam, sc.flat)) return e;
+  const Knobs kn = read_knobs();
+  c.lists_used = 0;
+  HIPCHK(hipMemsetAsync(c.counters, 0, COUNTER_WORDS * sizeof(unsigned long long), stream), "hipMemsetAsync");
+  if (ev0) HIPCHK(hipEventRecord(ev0, stream), "hipEventRecord");
+  // no sample or no depth: every sample is black (lib.rs:83 / :98), and x + 0 would only turn a -0 into +0
+  if (ts.n && f.spp && f.max_depth) {
+    uint32_t firsts[SAMPLE_BLOCKS_MAX], log2s[SAMPLE_BLOCKS_MAX];
+    const uint32_t nb = sample_blocks(sample_first, f.spp, firsts, log2s);
+    const uint32_t* lists = nullptr;
+    if (int e = frame_tile_lists(sc, c, f, stream, &lists)) return e;
+    // the sample buffer for the largest block, once: no block's run_passes then frees what an earlier one reads
+    const uint32_t big = *std::max_element(log2s, log2s + nb);
+    if (int e = grow(c.sbuf, sample_buffer_bytes(kn, ts.n, 1u << big))) return e;
+    const Film film{d_sq};
+    for (uint32_t k = 0; k < nb; ++k) {
+      Frame fb = f;
+      fb.spp = 1u << log2s[k];
+      fb.sample_base = firsts[k];
+      RenderArgs a = frame_args(c, fb, ts, d_sum);
+      a.tile_lists = lists;
+      // (the counters' reset above zeroed the dispensers for the first block; the statistics words run on)
+      if (k) HIPCHK(hipMemsetAsync(a.queue, 0, DISP * DISP_STRIDE * sizeof(unsigned long long), stream),
+                    "hipMemsetAsync(queue)");
+      if (int e = run_passes(sc, c, a, kn, ts.n, flags & RTW_FLAG_COUNT_TRAVERSAL, stream, &film)) return e;
+    }
+  }
+  if (ev1) HIPCHK(hipEventRecord(ev1, stream), "hipEventRecord");
+  return RTW_OK;
+}
+
+int enqueue_tonemap(const float* d_sum, uint32_t n_pixels, uint32_t spp, uint8_t* d_rgb8, hipStream_t stream) {
+  if (!n_pixels) return RTW_OK;
+  const float scale = 1.0f / (float)spp;  // rtw_tonemap's
+  const uint32_t grid = (uint32_t)(((uint64_t)n_pixels + dev::FILM_BLOCK - 1u) / dev::FILM_BLOCK);
+  hipLaunchKernelGGL(dev::tonemap_kernel, dim3(grid), dim3(dev::FILM_BLOCK), 0, stream, d_sum, n_pixels, scale, d_rgb8);
+  HIPCHK(hipGetLastError(), "tonemap_kernel launch");
   return RTW_OK;
 }
 

@@ -2,8 +2,9 @@
 // the grow-only buffers), the render calls' shared opening (check_frame, need_copy) and the frame checks it shares with
 // the camera-ray calls, statistics, the traversal guard's error word, and the render / status / diagnostic entry points
 // of one device.  Plain HIP runtime API: the kernels, which variant a scene runs and how a render is enqueued are
-// rtw_kernel.hip's (enqueue_render, enqueue_unpack); the six ray-query calls are rtw_query.cpp's, the render over
-// several devices rtw_multi.cpp's.
+// rtw_kernel.hip's (enqueue_render, enqueue_render_samples, enqueue_tonemap, enqueue_unpack); the six ray-query calls
+// are rtw_query.cpp's, the render over several devices rtw_multi.cpp's.  The progressive calls
+// (rtw_render_samples_device, rtw_sample_blocks, rtw_render_progressive, rtw_tonemap_device) are here too.
 #include <math.h>
 #include <string.h>
 
@@ -120,7 +121,7 @@ void release(Scene& s) {
     if (c.err_host) hipHostFree(c.err_host);
     if (c.lists_count) hipFree(c.lists_count);
     for (DevBuf* b : {&c.sbuf, &c.spill, &c.image, &c.tiles, &c.packed, &c.gathered, &c.gather_ids, &c.qrays, &c.qhits,
-                       &c.mshade, &c.qscatter, &c.qsamples, &c.pboxes, &c.tile_lists})
+                       &c.mshade, &c.qscatter, &c.qsamples, &c.pboxes, &c.tile_lists, &c.film_sum, &c.film_sq})
       free_buf(*b);
     for (hipEvent_t e : {c.ev[0], c.ev[1], c.gev[0], c.gev[1]})
       if (e) hipEventDestroy(e);
@@ -146,9 +147,9 @@ int grow(DevBuf& b, size_t bytes) {
   return RTW_OK;
 }
 
-int check_frame(const rtw_scene* s, const Frame& f, bool out) {
+int check_frame(const rtw_scene* s, const Frame& f, bool out, bool flattened_serves) {
   if (!s || !f.cam || !f.bg || !out) return fail(RTW_EINVAL, "NULL argument");
-  if (!s->s.committed) return fail(RTW_ESTATE, "scene not committed");
+  if (!(flattened_serves ? s->s.flattened : s->s.committed)) return fail(RTW_ESTATE, "scene not committed");
   return check_image_min(f.w, f.h);
 }
 
@@ -167,6 +168,13 @@ int check_shutter(const rtw_camera& cam, const Flat& f) {
   if (cam.time0 < f.time_lo || cam.time1 > f.time_hi)
     return fail(RTW_EINVAL, "camera shutter [%g, %g) outside the committed motion range [%g, %g]", cam.time0, cam.time1,
                 f.time_lo, f.time_hi);
+  return RTW_OK;
+}
+
+// the sample calls' range: the sample index is the path key's low word, and a block's size a uint32_t
+static int check_sample_range(uint32_t first, uint32_t n) {
+  if ((uint64_t)first + n > (1ull << 31))
+    return fail(RTW_EINVAL, "samples [%u, %u + %u) go beyond 2^31", first, first, n);
   return RTW_OK;
 }
 
@@ -302,6 +310,109 @@ int rtw_render_device_strided(rtw_scene* s, int device, const rtw_camera* cam, c
                 (unsigned long long)nt);
   const TileSet ts{nullptr, first_tile, tile_stride, n_tiles, true};
   return render_device(s, device, f, ts, d_out, abi_stream(stream), flags, stats);
+}
+
+int rtw_render_samples_device(rtw_scene* s, int device, const rtw_camera* cam, const float bg[3], uint32_t w,
+                              uint32_t h, uint32_t sample_first, uint32_t n_samples, uint32_t max_depth,
+                              uint64_t seed, const uint32_t* d_tiles, uint32_t n_tiles, float* d_sum, float* d_sq,
+                              void* stream, uint32_t flags, rtw_stats* stats) {
+  auto t0 = std::chrono::steady_clock::now();
+  const Frame f{cam, bg, w, h, n_samples, max_depth, seed};
+  if (int e = check_frame(s, f, d_sum, true)) return e;
+  if (int e = check_sample_range(sample_first, n_samples)) return e;
+  DeviceCopy* c = need_copy(s->s, device);
+  if (!c) return RTW_ENODEV;
+  const TileSet ts{d_tiles, 0, 1, d_tiles ? n_tiles : (uint32_t)f.tiles()};
+  DeviceGuard g;
+  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
+  if (stats)
+    if (int e = copy_events(*c)) return e;
+  const hipEvent_t e0 = stats ? c->ev[0] : nullptr, e1 = stats ? c->ev[1] : nullptr;
+  const hipStream_t st = abi_stream(stream);
+  int rc = enqueue_render_samples(s->s, *c, f, sample_first, ts, d_sum, d_sq, st, flags, e0, e1);
+  if (rc == RTW_OK && stats) {
+    rtw_stats out{};
+    rc = collect_stats(*c, st, e0, e1, (uint64_t)ts.n * 64u * n_samples, &out);
+    out.total_ms = ms_since(t0);
+    *stats = out;
+  }
+  return rc;
+}
+
+int rtw_sample_blocks(uint32_t sample_first, uint32_t n_samples, uint32_t* first, uint32_t* log2, uint32_t cap,
+                      uint32_t* n_blocks) {
+  if (!n_blocks || (cap && (!first || !log2))) return fail(RTW_EINVAL, "NULL argument");
+  if (int e = check_sample_range(sample_first, n_samples)) return e;
+  uint32_t firsts[SAMPLE_BLOCKS_MAX], log2s[SAMPLE_BLOCKS_MAX];
+  const uint32_t nb = sample_blocks(sample_first, n_samples, firsts, log2s);
+  *n_blocks = nb;
+  if (cap < nb) return fail(RTW_EINVAL, "samples [%u, %u + %u) are %u blocks: cap %u", sample_first, sample_first,
+                            n_samples, nb, cap);
+  for (uint32_t k = 0; k < nb; ++k) {
+    first[k] = firsts[k];
+    log2[k] = log2s[k];
+  }
+  return RTW_OK;
+}
+
+int rtw_render_progressive(rtw_scene* s, const rtw_camera* cam, const float bg[3], uint32_t w, uint32_t h,
+                           uint32_t spp, uint32_t max_depth, uint64_t seed, uint32_t step,
+                           int (*sink)(const float* rgb_sum, const float* rgb_sq_sum, uint32_t w, uint32_t h,
+                                       uint32_t samples_done, void* user),
+                           void* user, rtw_stats* stats) {
+  auto t0 = std::chrono::steady_clock::now();
+  const Frame f{cam, bg, w, h, spp, max_depth, seed};
+  if (int e = check_frame(s, f, sink, true)) return e;
+  if (int e = check_sample_range(0, spp)) return e;
+  DeviceCopy* c = need_copy(s->s, -1, nullptr);
+  if (!c) return RTW_ENODEV;
+  DeviceGuard g;
+  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
+  const size_t n = (size_t)w * h * 3, bytes = n * sizeof(float);
+  if (int e = copy_events(*c)) return e;
+  if (int e = grow(c->film_sum, bytes)) return e;  // kept for the next frame, as rtw_render's image
+  if (int e = grow(c->film_sq, bytes)) return e;
+  float* d_sum = static_cast<float*>(c->film_sum.p);
+  float* d_sq = static_cast<float*>(c->film_sq.p);
+  HIPCHK(hipMemsetAsync(d_sum, 0, bytes, nullptr), "hipMemsetAsync(sums)");
+  HIPCHK(hipMemsetAsync(d_sq, 0, bytes, nullptr), "hipMemsetAsync(sums of squares)");
+  std::vector<float> sum(n), sq(n);
+  const TileSet all{nullptr, 0, 1, (uint32_t)f.tiles()};
+  rtw_stats tot{};
+  int rc = RTW_OK;
+  for (uint32_t done = 0; rc == RTW_OK && done < spp;) {
+    // 1, 2, 4, ... while the doubled count stays within `step` (0: always), then `step` more at a time; the frame's
+    // last step ends at spp
+    const uint64_t next = !done ? 1u : ((!step || 2ull * done <= step) ? 2ull * done : (uint64_t)done + step);
+    const uint32_t end = (uint32_t)std::min<uint64_t>(next, spp);
+    Frame chunk = f;
+    chunk.spp = end - done;
+    rc = enqueue_render_samples(s->s, *c, chunk, done, all, d_sum, d_sq, nullptr, 0, c->ev[0], c->ev[1]);
+    rtw_stats st{};
+    if (rc == RTW_OK) rc = collect_stats(*c, nullptr, c->ev[0], c->ev[1], 0, &st);
+    if (rc == RTW_OK && (hipMemcpy(sum.data(), d_sum, bytes, hipMemcpyDeviceToHost) != hipSuccess ||
+                         hipMemcpy(sq.data(), d_sq, bytes, hipMemcpyDeviceToHost) != hipSuccess))
+      rc = fail(RTW_ENODEV, "hipMemcpy(sums)");
+    if (rc != RTW_OK) break;
+    done = end;
+    tot.rays += st.rays;
+    tot.kernel_ms += st.kernel_ms;
+    tot.paths = (uint64_t)w * h * done;
+    if (int e = sink(sum.data(), sq.data(), w, h, done, user)) rc = e;
+  }
+  tot.total_ms = ms_since(t0);
+  if (stats) *stats = tot;
+  return rc;
+}
+
+int rtw_tonemap_device(int device, const float* d_rgb_sum, uint32_t n_pixels, uint32_t spp, uint8_t* d_rgb8,
+                       void* stream) {
+  if ((!d_rgb_sum || !d_rgb8) && n_pixels) return fail(RTW_EINVAL, "NULL buffer");
+  if (spp == 0) return fail(RTW_EINVAL, "spp must be > 0");
+  if (!n_pixels) return RTW_OK;
+  DeviceGuard g;
+  if (device >= 0) HIPCHK(hipSetDevice(device), "hipSetDevice");
+  return enqueue_tonemap(d_rgb_sum, n_pixels, spp, d_rgb8, abi_stream(stream));
 }
 
 int rtw_render_status(rtw_scene* s, int device) {

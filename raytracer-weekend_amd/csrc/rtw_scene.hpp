@@ -123,6 +123,7 @@ struct DeviceCopy {
   // device buffers kept across render calls (grown, never shrunk; freed by release()): a
   // 30-camera animation through rtw_render does no hipMalloc after the first frame
   DevBuf image, tiles, packed, gathered, gather_ids;
+  DevBuf film_sum, film_sq;                // rtw_render_progressive's device sums: the frame's Σ x and Σ x^2
   DevBuf qrays, qhits;                     // rtw_hit_rays' staging: one chunk of rays and of records
   DevBuf mshade;                           // Flat::mshade (uploaded with the scene; scatter_kernel's material table)
   DevBuf qscatter;                         // rtw_scatter_rays' staging: one chunk of rtw_scatter records
@@ -200,6 +201,9 @@ struct Frame {
   const float* bg;
   uint32_t w, h, spp, max_depth;
   uint64_t seed;
+  // host only: the frame's sample s is sample sample_base + s of its pixel.  A multiple of spp, itself a power of two,
+  // so that sample_base + s == sample_base ^ s: frame_args folds it into the path key (enqueue_render_samples' blocks)
+  uint32_t sample_base = 0;
   uint32_t tiles_x() const { return (w + 7u) / 8u; }
   // 8x8 pixel tiles, ragged edges whole (fits 32 bits for every image the render accepts: sides <= 65536)
   uint64_t tiles() const { return (uint64_t)((w + 7u) / 8u) * ((h + 7u) / 8u); }
@@ -224,8 +228,10 @@ void release(Scene& s);
 DeviceCopy* find_copy(Scene& s, int device);  // device < 0: the first copy
 int grow(DevBuf& b, size_t bytes);            // current device; contents not kept
 // The render calls' argument checks, in this order: a NULL argument (RTW_EINVAL), an uncommitted scene (RTW_ESTATE),
-// an image under 2x2 (RTW_EINVAL).  `out` is the call's image, device pointer or sink.
-int check_frame(const rtw_scene* s, const Frame& f, bool out);
+// an image under 2x2 (RTW_EINVAL).  `out` is the call's image, device pointer or sink.  flattened_serves: the state
+// asked for is the ray queries' (rtw_scene_commit got past the flattener, with or without a device), so that the
+// progressive calls' later checks answer on a machine without a GPU, where the device copy is the last thing missing.
+int check_frame(const rtw_scene* s, const Frame& f, bool out, bool flattened_serves = false);
 // The frame checks one by one, each RTW_EINVAL, shared by the render calls (check_frame; enqueue_render, after the
 // device copy is found) and rtw_camera_rays*: an image under 2x2, a side over 65536, a shutter that leaves the
 // committed motion range
@@ -251,6 +257,20 @@ int64_t last_render_lists(Scene& s, int field);
 // ev0 / ev1 (or NULL) are recorded around it
 int enqueue_render(Scene& s, DeviceCopy& c, const Frame& f, const TileSet& tiles, float* d_out, hipStream_t stream,
                    uint32_t flags, hipEvent_t ev0, hipEvent_t ev1);
+// The aligned power-of-two blocks of the sample range [first, first + n), first + n <= 2^31, in ascending order: block
+// k = [firsts[k], firsts[k] + 2^log2s[k]) with firsts[k] a multiple of its size, each the largest such block that
+// starts where the one before ended and fits the range (greedy: at most SAMPLE_BLOCKS_MAX of them).  -> their number
+constexpr uint32_t SAMPLE_BLOCKS_MAX = 62;
+uint32_t sample_blocks(uint32_t first, uint32_t n, uint32_t* firsts, uint32_t* log2s);
+// enqueue samples [sample_first, sample_first + f.spp) of the tiles' pixels, ADDED in sample order onto what d_sum and
+// d_sq (or NULL) hold, on `stream` of c.device, which must be current: enqueue_render's checks, counters and tile lists
+// once, then one round of passes per block of sample_blocks, each pass's in-order reduction continuing the sums.
+// Nothing is enqueued but the counters' reset for f.spp == 0 or f.max_depth == 0.  The caller has checked the range.
+int enqueue_render_samples(Scene& s, DeviceCopy& c, const Frame& f, uint32_t sample_first, const TileSet& tiles,
+                           float* d_sum, float* d_sq, hipStream_t stream, uint32_t flags, hipEvent_t ev0,
+                           hipEvent_t ev1);
+// enqueue rtw_tonemap over device arrays (n_pixels x rgb sums -> n_pixels x rgb8) on `stream` of the current device
+int enqueue_tonemap(const float* d_sum, uint32_t n_pixels, uint32_t spp, uint8_t* d_rgb8, hipStream_t stream);
 // enqueue one closest-hit query of n rays (rtw_ray[n] -> rtw_hit[n], device arrays) on `stream` of c.device, which
 // must be current; ev0 / ev1 (or NULL) are recorded around the kernel
 int enqueue_hit_rays(Scene& s, DeviceCopy& c, uint64_t n, const void* d_rays, void* d_hits, hipStream_t stream,
