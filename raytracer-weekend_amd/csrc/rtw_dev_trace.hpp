@@ -288,9 +288,9 @@ constexpr bool far_kernel_feat(uint32_t feat) {
 // borrows the lane's column.  A lane whose segment needs the far-origin walk takes it here, instead of the main walk.
 // RING (the 1024-lane sphere kernel's start ring, path_kernel): `start` is what the lane's ring entry decided for this
 // segment -- a primitive index (the segment's closest hit: the lane tests that primitive alone, so ts.b gets the same
-// t from the same test, and takes no root), -1 (a miss: no test, no root) or -3 (undecided, and every later segment: the
-// always list and the walk as ever).  One loop serves all three, the index per lane, so a decided lane adds no
-// instruction stream of its own.
+// t from the same test, and takes no root) or -3 (undecided, and every later segment: the always list and the walk as
+// ever); a start that the ring's make resolved to a miss never gets here (the make retires it).  One loop serves both,
+// the index per lane, so a decided lane adds no instruction stream of its own.
 template <bool COUNT, uint32_t FEAT, int STACK = 1, int BLK = BLOCK, bool C16 = false, int NCAP = 0, bool RING = false>
 __device__ __forceinline__ void trace_begin(const DevScene& S, const Ray& r, TraceState& ts, uint32_t* cnt,
                                             uint64_t seg, uint16_t* stk16 = nullptr, int32_t* stk = nullptr,
@@ -324,7 +324,7 @@ __device__ __forceinline__ void trace_begin(const DevScene& S, const Ray& r, Tra
     // (measured against a second form -- every lane the scalar always loop, then the lanes whose winner is a BVH
     // primitive one more test of their own -- this one loop was 1.6% faster: profiles/r08/experiments)
     const SphRcp rq = sph_rcp(r);
-    const uint32_t n = decided ? (start >= 0 ? 1u : 0u) : S.n_always;
+    const uint32_t n = decided ? 1u : S.n_always;
     for (uint32_t k = 0; __any(k < n); ++k) {
       if (k < n) {
         const uint32_t pi = decided ? (uint32_t)start : uload(S.always + k);

@@ -88,6 +88,10 @@ struct StartMade {
 // What a ring entry knows of its path's first segment (the per-tile lists, rtw_tile_beam.h): the closest hit's
 // primitive index (>= 0), START_MISS (nothing hit), or START_WALK (not decided: the segment walks the tree)
 constexpr int32_t START_MISS = -1, START_WALK = -3;
+// The ring entry's winner word: the winner in the low half (RING_WALK for START_WALK: the lists' primitive indices are
+// below TILE_LIST_OVER, the same value), the path's lane of origin in the make (id = the ring's first id + it) above.
+// A START_MISS path is never stored: the make writes its sample (path_kernel).
+constexpr uint32_t RING_WALK = 0xFFFFu;
 template <bool FROM_LDS, bool AB>
 __device__ __forceinline__ bool start_make(const StartArgs& a, uint64_t pid, StartMade& m) {
   if constexpr (FROM_LDS) asm volatile("" ::: "memory");  // read the LDS copy here: no loop-invariant register copies
@@ -358,7 +362,11 @@ __global__ __launch_bounds__(K.blk) __attribute__((amdgpu_waves_per_eu(K.occ, 8)
   // The 1024-lane LDS-node sphere kernel (K.ldsn_ring()) has 1.75 KB per wave beside its stack and node table: a 7-word
   // entry, start_make's half of the start -- rd.x, rd.y, u, v, rng before the time draw -- with the first segment's
   // closest hit where the tile's list decides it (start_decide), and the ring's first id once per wave (an entry's id
-  // is that + its index); the lanes that take an entry finish it with start_take.
+  // is that + its lane of origin, kept beside the winner); the lanes that take an entry finish it with start_take.
+  // The make stores live entries only, packed against the ring's top (head = 64 - their count): an off-image id stores
+  // nothing, and a camera ray that the list resolves to a miss is retired by the make itself, which writes its sample
+  // and counts its one segment.  A make may so yield fewer entries than the idle lanes want, or none (a sky tile):
+  // those lanes stay idle and the wave regenerates again, until its pool and the dispensers are dry.
   // (the other LDS-node and the mesh kernels have no LDS left for a ring at their occupancy)
   // Its head and first id follow the wave's entries (RS words per wave), so one address serves all three.
   constexpr uint32_t RW = K.ring_words(), RS = RW * 64u + (K.ldsn_ring() ? 2u : 0u);
@@ -414,11 +422,12 @@ __global__ __launch_bounds__(K.blk) __attribute__((amdgpu_waves_per_eu(K.occ, 8)
           if constexpr (K.ldsn_ring()) {  // the 7-word entry: start_take finishes it
             const uint32_t lo = ring[5 * 64 + e], hi = ring[6 * 64 + e];
             const float rdx = __uint_as_float(ring[e]), rdy = __uint_as_float(ring[64 + e]);
+            const uint32_t ww = ring[4 * 64 + e];  // winner | lane of origin << 16
             start_take<true, K.alignbit_draws()>(SA, rdx, rdy, __uint_as_float(ring[2 * 64 + e]),
                                                  __uint_as_float(ring[3 * 64 + e]), ((uint64_t)hi << 32) | lo,
-                                                 ring_base[0] + e, st);
-            start_win = (int32_t)ring[4 * 64 + e];
-            has = (lo | hi) != 0u;
+                                                 ring_base[0] + (ww >> 16), st);
+            start_win = (ww & 0xFFFFu) == RING_WALK ? START_WALK : (int32_t)(ww & 0xFFFFu);
+            has = true;  // the ring holds live entries only
           } else {
             const uint32_t lo = ring[7 * 64 + e], hi = ring[8 * 64 + e];
             st.ray.o = mk(__uint_as_float(ring[e]), __uint_as_float(ring[64 + e]), __uint_as_float(ring[2 * 64 + e]));
@@ -450,17 +459,44 @@ __global__ __launch_bounds__(K.blk) __attribute__((amdgpu_waves_per_eu(K.occ, 8)
           // enqueue_render; the automatic halving stays on powers of two >= 128) and n_paths = slots x 64 x spp
           if (pool_next < pool_end) {
             const uint64_t id = pool_next + lane;
+            [[maybe_unused]] uint32_t n_made = 64u;  // K.ldsn_ring(): the entries this make stores (wave-uniform)
             if constexpr (K.ldsn_ring()) {
               StartMade m;
               const bool ok = start_make<K.start_args_in_lds(), K.alignbit_draws()>(SA, id, m);
               const int32_t win = start_decide<COUNT, K.feat, K.alignbit_draws()>(S, SA, a.tile_lists, m, cnt);
-              ring[lane] = __float_as_uint(m.rdx);
-              ring[64 + lane] = __float_as_uint(m.rdy);
-              ring[2 * 64 + lane] = __float_as_uint(m.u);
-              ring[3 * 64 + lane] = __float_as_uint(m.v);
-              ring[4 * 64 + lane] = (uint32_t)win;
-              ring[5 * 64 + lane] = ok ? (uint32_t)m.rng : 0u;
-              ring[6 * 64 + lane] = ok ? (uint32_t)(m.rng >> 32) : 0u;
+              // a camera ray that hits nothing is finished here: its sample is the miss branch's T * bg with T = 1, one
+              // segment; the wave's 64 ids are consecutive, so a sky tile's samples are 768 contiguous bytes
+              const bool sky = ok && win == START_MISS;
+              if (sky) {
+                const V3 L = mul(mk(1.f, 1.f, 1.f), bg);
+                float* o = a.sbuf + (size_t)(uint32_t)id * 3u;
+#if RTW_NT_SAMPLES
+                __builtin_nontemporal_store(L.x, o);
+                __builtin_nontemporal_store(L.y, o + 1);
+                __builtin_nontemporal_store(L.z, o + 2);
+#else
+                o[0] = L.x;
+                o[1] = L.y;
+                o[2] = L.z;
+#endif
+              }
+              nrays += (unsigned long long)__popcll(__ballot(sky));
+              // the live entries (on the image, not retired) packed against the ring's top: head = 64 - n_live
+              const bool live = ok && !sky;
+              const uint64_t lv = __ballot(live);
+              n_made = (uint32_t)__popcll(lv);
+              const uint32_t e = 64u - n_made +
+                                 __builtin_amdgcn_mbcnt_hi((uint32_t)(lv >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)lv, 0u));
+              if (live) {
+                ring[e] = __float_as_uint(m.rdx);
+                ring[64 + e] = __float_as_uint(m.rdy);
+                ring[2 * 64 + e] = __float_as_uint(m.u);
+                ring[3 * 64 + e] = __float_as_uint(m.v);
+                // (an always-list winner past 16 bits walks instead: the lists' own primitives are below RING_WALK)
+                ring[4 * 64 + e] = ((uint32_t)win < RING_WALK ? (uint32_t)win : RING_WALK) | (lane << 16);
+                ring[5 * 64 + e] = (uint32_t)m.rng;
+                ring[6 * 64 + e] = (uint32_t)(m.rng >> 32);
+              }
               if (lane == 0) ring_base[0] = (uint32_t)pool_next;
             } else {
               PathState g;
@@ -477,8 +513,16 @@ __global__ __launch_bounds__(K.blk) __attribute__((amdgpu_waves_per_eu(K.occ, 8)
               ring[9 * 64 + lane] = (uint32_t)id;
             }
             pool_next += 64u;
-            if (!has && !first) take(rank - have);
-            head = n_need - have;
+            // (K.ldsn_ring(): a make may yield fewer than the takers want, or none: they stay idle, and the wave
+            // regenerates again under the usual rule)
+            if constexpr (K.ldsn_ring()) {
+              const uint32_t head0 = 64u - n_made, want = n_need - have;
+              if (!has && !first && rank - have < n_made) take(head0 + (rank - have));
+              head = head0 + (want < n_made ? want : n_made);
+            } else {
+              if (!has && !first) take(rank - have);
+              head = n_need - have;
+            }
           } else {
             exhausted = true;  // no ids left: the ring stays empty
             head = 64u;
