@@ -29,7 +29,22 @@ class oracle_camera(C.Structure):
 
 _F = C.POINTER(C.c_float)
 _U32 = C.POINTER(C.c_uint32)
+_U64 = C.POINTER(C.c_uint64)
 _lib = None
+
+# The records of the caller-ray entries (rtw_oracle.h: oracle_hit, oracle_scattered, oracle_sample).  Fields are named
+# as the product's HIT_DTYPE, SCATTER_DTYPE + RAY_DTYPE and SAMPLE_DTYPE name them, and the flag values are the product's.
+HIT_HIT, HIT_FRONT_FACE = 1, 2
+SCATTER_SCATTERED, SCATTER_MISS = 1, 2
+END_MISS, END_NO_SCATTER, END_DEPTH = 1, 2, 8
+HIT_RECORD = np.dtype([("p", np.float32, 3), ("normal", np.float32, 3), ("t", np.float32), ("u", np.float32),
+                       ("v", np.float32), ("material", np.uint32), ("flags", np.uint32)])
+SCATTER_RECORD = np.dtype([("attenuation", np.float32, 3), ("emitted", np.float32, 3), ("origin", np.float32, 3),
+                           ("direction", np.float32, 3), ("time", np.float32), ("flags", np.uint32),
+                           ("stream", np.uint64)])
+SAMPLE_RECORD = np.dtype([("color", np.float32, 3), ("segments", np.uint32), ("stream", np.uint64),
+                          ("flags", np.uint32), ("reserved", np.uint32)])
+assert (HIT_RECORD.itemsize, SCATTER_RECORD.itemsize, SAMPLE_RECORD.itemsize) == (44, 64, 32)
 
 
 def build() -> None:
@@ -76,6 +91,10 @@ def lib() -> C.CDLL:
             "oracle_medium_hit": (C.c_int, [C.c_int, _F, C.c_float, _F, C.c_float, C.c_float, C.c_uint64,
                                             C.c_uint32, _F]),
             "oracle_noise": (C.c_float, [_F, C.POINTER(C.c_int32), _F, C.c_int]),
+            "oracle_hit_rays": (C.c_int, [C.c_void_p, C.c_uint64, _F, _U64, C.c_int, C.c_void_p, C.c_void_p]),
+            "oracle_scatter_rays": (C.c_int, [C.c_void_p, C.c_uint64, _F, _U64, C.c_void_p, _F, C.c_void_p]),
+            "oracle_sample_rays": (C.c_int, [C.c_void_p, C.c_uint64, _F, _U64, _F, C.c_uint32, C.c_int, C.c_int,
+                                             C.c_void_p]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -122,8 +141,8 @@ class OracleScene:
             raise RuntimeError(lib().oracle_last_error().decode())
 
     def __del__(self):
-        if getattr(self, "_p", None):
-            lib().oracle_scene_free(self._p)
+        if getattr(self, "_p", None) and _lib is not None:  # (None at interpreter exit, where module-level caches
+            _lib.oracle_scene_free(self._p)                 # of scenes are collected after this module's globals)
             self._p = None
 
     def count(self, what: int) -> int:
@@ -159,6 +178,47 @@ class OracleScene:
         if rc != 0:
             raise RuntimeError(lib().oracle_last_error().decode())
         return out, int(rays.value)
+
+    # ---- rays the caller chooses (records with origin, direction, time and stream fields, as the product's RAY_DTYPE)
+    @staticmethod
+    def _rays(rays):
+        r7 = np.ascontiguousarray(np.concatenate([rays["origin"], rays["direction"], rays["time"][:, None]], axis=1),
+                                  np.float32)
+        return r7, np.ascontiguousarray(rays["stream"], np.uint64)
+
+    def _check(self, rc):
+        if rc != 0:
+            raise RuntimeError(lib().oracle_last_error().decode())
+
+    def hit_rays(self, rays, bvh_mode=BVH_AS_LIST, ties=False):
+        """world.hit(ray, 0.001, inf) per ray -> HIT_RECORD records (material: the index in the dump's table)[, a bool
+        per ray: two or more objects hit at the winner's t exactly]."""
+        r7, st = self._rays(rays)
+        out = np.zeros(len(r7), HIT_RECORD)
+        tie = np.zeros(len(r7), np.uint8)
+        self._check(lib().oracle_hit_rays(self._p, len(r7), fp(r7), st.ctypes.data_as(_U64), bvh_mode, out.ctypes.data,
+                                          tie.ctypes.data if ties else None))
+        return (out, tie != 0) if ties else out
+
+    def scatter_rays(self, rays, hits, background) -> np.ndarray:
+        """Material::emitted + scatter for (ray, hit record) pairs -> SCATTER_RECORD records.  hits: records with
+        HIT_RECORD's fields (the product's HIT_DTYPE has them)."""
+        r7, st = self._rays(rays)
+        h = np.zeros(len(r7), HIT_RECORD)
+        for name in HIT_RECORD.names:
+            h[name] = hits[name]
+        out = np.zeros(len(r7), SCATTER_RECORD)
+        self._check(lib().oracle_scatter_rays(self._p, len(r7), fp(r7), st.ctypes.data_as(_U64), h.ctypes.data,
+                                              fp(f32(background)), out.ctypes.data))
+        return out
+
+    def sample_rays(self, rays, background, max_depth=50, integrator=ITERATIVE, bvh_mode=BVH_AS_LIST) -> np.ndarray:
+        """sample_ray per ray -> SAMPLE_RECORD records (the product's SAMPLE_DTYPE, field for field)."""
+        r7, st = self._rays(rays)
+        out = np.zeros(len(r7), SAMPLE_RECORD)
+        self._check(lib().oracle_sample_rays(self._p, len(r7), fp(r7), st.ctypes.data_as(_U64), fp(f32(background)),
+                                             max_depth, integrator, bvh_mode, out.ctypes.data))
+        return out
 
 
 def libm(fn: int, a, b=None) -> np.ndarray:

@@ -1451,3 +1451,127 @@ int oracle_medium_hit(int kind, const float* params, float density, const float 
   *t_out = h.t;
   return 1;
 }
+
+/* ------------------------------------------------------------------ rays the caller chooses
+ * world_hit, mat_emitted + mat_scatter and sample_ray_* above, for rays no camera made: wrappers only. */
+static draws draws_at(uint64_t stream) {
+  draws d;
+  memset(&d, 0, sizeof d);
+  d.rng.s = stream;
+  return d;
+}
+static void put3(float* o, vec3 a) { o[0] = a.x; o[1] = a.y; o[2] = a.z; }
+static void put_ray(float* o, const ray* r) { put3(o, r->o); put3(o + 3, r->d); o[6] = r->time; }
+
+/* how many objects of the world answer world.hit's interval at exactly t: groups that leave the ray alone (lists,
+ * BvhNode groups, a Cuboid's sides) count member by member, a wrapper chain or a medium as the one object it is */
+static int count_at(const onode* nd, const ray* r, float t, int bvh_mode) {
+  if (nd->kind == K_LIST || nd->kind == K_BVH || nd->kind == K_CUBOID) {
+    int n = 0;
+    for (int k = 0; k < nd->n; ++k) n += count_at(nd->ch[k], r, t, bvh_mode);
+    return n;
+  }
+  hitrec h;
+  return node_hit(nd, r, 0.001f, INFINITY, bvh_mode, &h) && h.t == t;
+}
+
+int oracle_hit_rays(const oracle_scene* s, uint64_t n, const float* rays, const uint64_t* streams, int bvh_mode,
+                    oracle_hit* out, uint8_t* tie) {
+  if (!s || (n && (!rays || !streams || !out))) { set_err("bad arguments"); return -22; }
+  if (tie) memset(tie, 0, n);
+  ctx_t c = {s, v3(0, 0, 0), bvh_mode, 0};
+  for (uint64_t k = 0; k < n; ++k) {
+    const ray r = ray_from(rays + 7 * k);
+    const draws d = draws_at(streams[k]);
+    hitrec h;
+    oracle_hit* o = &out[k];
+    memset(&h, 0, sizeof h);
+    memset(o, 0, sizeof *o);
+    if (!world_hit(&c, &r, &d, &h)) { o->t = INFINITY; continue; }
+    put3(o->p, h.p);
+    put3(o->normal, h.n);
+    o->t = h.t; o->u = h.u; o->v = h.v;
+    o->material = (uint32_t)h.mat;
+    o->flags = ORACLE_HIT_HIT | (h.front ? ORACLE_HIT_FRONT_FACE : 0);
+    if (tie) tie[k] = count_at(s->root, &r, h.t, bvh_mode) > 1;
+  }
+  return 0;
+}
+
+int oracle_scatter_rays(const oracle_scene* s, uint64_t n, const float* rays, const uint64_t* streams,
+                        const oracle_hit* hits, const float background[3], oracle_scattered* out) {
+  if (!s || !background || (n && (!rays || !streams || !hits || !out))) { set_err("bad arguments"); return -22; }
+  for (uint64_t k = 0; k < n; ++k)
+    if ((hits[k].flags & ORACLE_HIT_HIT) && hits[k].material >= (uint32_t)s->nmat) {
+      set_err("material index outside the scene's table");
+      return -22;
+    }
+  for (uint64_t k = 0; k < n; ++k) {
+    const ray r = ray_from(rays + 7 * k);
+    const oracle_hit* q = &hits[k];
+    draws d = draws_at(streams[k]);
+    oracle_scattered* o = &out[k];
+    memset(o, 0, sizeof *o);
+    if (!(q->flags & ORACLE_HIT_HIT)) { /* lib.rs:102-105 */
+      put3(o->emitted, cv(background));
+      put_ray(o->ray, &r);
+      o->flags = ORACLE_SCATTER_MISS;
+      o->stream = d.rng.s;
+      continue;
+    }
+    hitrec h;
+    h.p = cv(q->p); h.n = cv(q->normal);
+    h.t = q->t; h.u = q->u; h.v = q->v;
+    h.mat = (int)q->material;
+    h.front = (q->flags & ORACLE_HIT_FRONT_FACE) != 0;
+    const omat* m = &s->mat[h.mat];
+    scatter_t sc;
+    sc.att = v3(0, 0, 0);
+    sc.out.o = h.p; sc.out.d = r.d; sc.out.time = r.time; /* a light makes no ray */
+    put3(o->emitted, mat_emitted(s, m, &h));               /* lib.rs:107 */
+    if (mat_scatter(s, m, &r, &h, &d, &sc)) {              /* lib.rs:109 */
+      put3(o->attenuation, sc.att);
+      o->flags = ORACLE_SCATTER_SCATTERED;
+    }
+    put_ray(o->ray, &sc.out);
+    o->stream = d.rng.s;
+  }
+  return 0;
+}
+
+int oracle_sample_rays(const oracle_scene* s, uint64_t n, const float* rays, const uint64_t* streams,
+                       const float background[3], uint32_t max_depth, int integrator, int bvh_mode,
+                       oracle_sample* out) {
+  if (!s || !background || (n && (!rays || !streams || !out))) { set_err("bad arguments"); return -22; }
+  g_trace = 0;
+  for (uint64_t k = 0; k < n; ++k) {
+    ctx_t c = {s, cv(background), bvh_mode, 0};
+    ray r = ray_from(rays + 7 * k);
+    draws d = draws_at(streams[k]);
+    const vec3 col = integrator == ORACLE_RECURSIVE ? sample_ray_rec(&c, &r, &d, max_depth)
+                                                    : sample_ray_iter(&c, r, &d, max_depth);
+    oracle_sample* o = &out[k];
+    memset(o, 0, sizeof *o);
+    put3(o->color, col);
+    o->segments = (uint32_t)c.rays;
+    o->stream = d.rng.s;
+    /* How the path ended: sample_ray returns a colour only, so its c.rays segments are walked again with the same
+     * functions and draws, without a colour; the last one is a miss, a hit that did not scatter, or -- having scattered,
+     * which only the max_depth-th segment can do last -- depth exhaustion. */
+    ctx_t c2 = {s, cv(background), bvh_mode, 0};
+    draws d2 = draws_at(streams[k]);
+    for (uint64_t q = 0; q < c.rays; ++q) {
+      hitrec h;
+      scatter_t sc;
+      if (!world_hit(&c2, &r, &d2, &h)) { o->flags = ORACLE_END_MISS; break; }
+      if (!mat_scatter(s, &s->mat[h.mat], &r, &h, &d2, &sc)) { o->flags = ORACLE_END_NO_SCATTER; break; }
+      r = sc.out;
+      if (q + 1 == c.rays) o->flags = ORACLE_END_DEPTH;
+    }
+    if (d2.rng.s != d.rng.s || c2.rays != c.rays || (o->flags == ORACLE_END_DEPTH && c.rays != max_depth)) {
+      set_err("the second walk of a path left sample_ray's");
+      return -71;
+    }
+  }
+  return 0;
+}

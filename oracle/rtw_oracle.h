@@ -68,6 +68,51 @@ int oracle_render_pixels(oracle_scene* s, const oracle_camera* cam, const float 
                          int integrator, int bvh_mode, int n_threads,
                          const uint32_t* px, uint32_t n_px, float* out, uint64_t* rays);
 
+/* ---- rays the caller chooses: world.hit, Material::emitted + scatter and sample_ray (lib.rs:97-117) of a parsed scene
+ *      for n rays that no camera made.  Ray k is rays[7k .. 7k+6] (origin, direction, time) and streams[k], the path
+ *      generator's state at the segment start: it keys the media (g_seg) and the materials draw from it.  The entries
+ *      wrap the render's own static functions and add no arithmetic.  Flag values are the product's (include/rtw.h). */
+enum { ORACLE_HIT_HIT = 1, ORACLE_HIT_FRONT_FACE = 2 };
+enum { ORACLE_SCATTER_SCATTERED = 1, ORACLE_SCATTER_MISS = 2 };
+enum { ORACLE_END_MISS = 1, ORACLE_END_NO_SCATTER = 2, ORACLE_END_DEPTH = 8 };
+/* hittable/mod.rs:22-29 HitRecord; material: the index in the scene's table.  A miss: flags 0, t +inf, zeros elsewhere.
+ * (No leaf key: the oracle has no committed hierarchy.) */
+typedef struct {
+  float p[3], normal[3];
+  float t, u, v;
+  uint32_t material, flags;
+} oracle_hit;
+/* material.rs:18-21 Scatter + Material::emitted.  ray: origin, direction, time of the ray to follow: origin p and the
+ * material's direction when one was made (an absorbed Metal ray's too); p and the incoming direction for a light (no ray
+ * to follow); the incoming ray itself for a miss.  stream: the generator state after the material's draws. */
+typedef struct {
+  float attenuation[3], emitted[3];
+  float ray[7];
+  uint32_t flags;
+  uint64_t stream;
+} oracle_scattered;
+/* sample_ray's value; segments: its world.hit calls; stream: the generator state at return; flags: how the path ended
+ * (0 when max_depth is 0) */
+typedef struct {
+  float color[3];
+  uint32_t segments;
+  uint64_t stream;
+  uint32_t flags, reserved;
+} oracle_sample;
+/* one world.hit(ray, 0.001, +inf) per ray (lib.rs:102).  tie (may be NULL): tie[k] = 1 when two or more objects of the
+ * world hit at the winner's t exactly (lists, BvhNode groups and a Cuboid's sides counted member by member; a wrapper
+ * chain or a medium as one object), found by testing each object alone over the same interval. */
+int oracle_hit_rays(const oracle_scene* s, uint64_t n, const float* rays, const uint64_t* streams, int bvh_mode,
+                    oracle_hit* out, uint8_t* tie);
+/* lib.rs:102-116 after world.hit: the background for a miss record; else mat_emitted, then mat_scatter drawing from the
+ * stream word.  Reads a record's p, normal, u, v, material and flags.  -22: a material index outside the table. */
+int oracle_scatter_rays(const oracle_scene* s, uint64_t n, const float* rays, const uint64_t* streams,
+                        const oracle_hit* hits, const float background[3], oracle_scattered* out);
+/* sample_ray per ray with the generator at streams[k]: ORACLE_ITERATIVE or ORACLE_RECURSIVE */
+int oracle_sample_rays(const oracle_scene* s, uint64_t n, const float* rays, const uint64_t* streams,
+                       const float background[3], uint32_t max_depth, int integrator, int bvh_mode,
+                       oracle_sample* out);
+
 /* ---- unit-level entry points used by the KAT / golden-vector tests ---- */
 uint32_t oracle_pcg32_stream(uint64_t state, uint32_t n, uint32_t* out, uint64_t* state_out);
 uint32_t oracle_rng_stream(uint64_t state, uint32_t n, uint32_t* out, uint64_t* state_out);

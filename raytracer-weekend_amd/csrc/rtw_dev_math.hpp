@@ -268,10 +268,20 @@ __device__ __forceinline__ float dev_acosf(float x) {  // f32::acos = atan2(sqrt
 // integers in [1, 65535] and dividends 0 or in [2^-24, 65536), with y computed exactly on the host.
 // Three VALU ops instead of the ~10 of an IEEE division; tests/test_gpu_parity.py checks it against
 // IEEE division on the device.
+// The residual is formed negated, t = q0 b - x = -r, and taken off again: the same roundings for every x != 0 (fma
+// rounds to nearest, which is symmetric), the same three VALU ops (the negations are source modifiers), and over a
+// positive divisor -- a length in unit(), w - 1 and h - 1 in the camera -- a zero x keeps its sign as an IEEE quotient
+// does.  With r = fma(-q0, b, x) a dividend of -0 gave q0 = -0, r = +0 + -0 = +0 and fma(+0, y, -0) = +0: unit() turned
+// a direction component of -0 into +0, which Metal's and the Dielectric's reflected rays then carried
+// (tests/test_gpu_ray_corpus.py::test_unit_keeps_the_sign_of_a_zero_component).  Over a negative divisor a dividend of
+// +0 gives +0 where IEEE gives -0 (no three-op form is right for both signs of b: the residual of a zero dividend is
+// +0 whatever its sign).  So the hit record's (p - c) / r, whose r is negative for a hollow sphere, divides by |r| with
+// r's sign folded into the dividend (rtw_dev_shade.hpp); the rect test, the other signed divisor, rejects t = +-0
+// alike, below t_min.
 __device__ __forceinline__ float div_by_recip(float x, float b, float y) {
   const float q0 = x * y;
-  const float r = __builtin_fmaf(-q0, b, x);
-  return __builtin_fmaf(r, y, q0);
+  const float t = __builtin_fmaf(q0, b, -x);
+  return __builtin_fmaf(-t, y, q0);
 }
 // RN(1 / b) in three VALU ops: the hardware reciprocal (v_rcp_f32, within 1 ulp) refined by one Newton
 // step with an exact residual, e = 1 - b y0 (fma), y1 = RN(y0 + e y0).  Equal to the IEEE quotient 1.0f / b

@@ -90,9 +90,16 @@ __device__ Rec hit_record(const DevScene& S, const Ray& wr, const Best& b, uint3
     V3 c = type == PT_SPHERE ? mk(q0.x, q0.y, q0.z) : center_at(q0, q1, PP, S.msphere_unit, lr.time);
     const float rad = q2.z;  // r (q0.w holds r * r)
     // spherical.rs:49 (p - c) / r by the corrections from RN(1 / r), computed once by the flattener (q2.w)
+    // The correction keeps a zero dividend's sign only over a positive divisor (div_by_recip), and a hollow sphere's r
+    // is negative: x / r = (x with r's sign folded in) / |r|, signed zeros included, so the dividend takes the sign
+    // and |r|, |1 / r| divide (p.x == c.x exactly is common where the coordinates are coarse: the offset worlds)
     const V3 pc = sub(h.p, c);
+    const uint32_t rs = __float_as_uint(rad) & 0x80000000u;
+    const float ar = fabsf(rad), ay = fabsf(q2.w);
     const bool ok = recip_div_ok(rad);
-    outward = mk(div_rcp(pc.x, rad, q2.w, ok), div_rcp(pc.y, rad, q2.w, ok), div_rcp(pc.z, rad, q2.w, ok));
+    outward = mk(div_rcp(__uint_as_float(__float_as_uint(pc.x) ^ rs), ar, ay, ok),
+                 div_rcp(__uint_as_float(__float_as_uint(pc.y) ^ rs), ar, ay, ok),
+                 div_rcp(__uint_as_float(__float_as_uint(pc.z) ^ rs), ar, ay, ok));
     if ((FEAT & F_UV) && (shade_kind & (1u << 12))) sphere_uv(outward, h.u, h.v);
   } else if ((FEAT & F_TRI) && type == PT_TRI) {
     const TriUV s{b.t, b.u, b.v};  // tri_solve's values from the winning test (the same ray and operands)

@@ -87,7 +87,9 @@ def test_random_world_bit_exact(gpu, orc, seed):
     _random_world(gpu, orc, seed, W, H, SPP)
 
 
-def _random_world(rtw, orc, seed, W, H, SPP, max_depth=50):
+def mixed_world(rtw, seed, W, H):
+    """-> (the uncommitted scene of mixed world `seed`, its camera for a W x H frame, its background); imported by
+    tests/test_ray_corpus.py too"""
     rng = np.random.default_rng(1000 + seed)
     s = rtw.Scene()
     _build(rtw, s, rng)
@@ -95,6 +97,11 @@ def _random_world(rtw, orc, seed, W, H, SPP, max_depth=50):
     cam = rtw.Camera.new(tuple(eye), tuple(rng.uniform(-1, 1, 3)), (0, 1, 0), float(rng.uniform(30, 70)), W / H,
                          float(rng.choice([0.0, 0.1])), float(np.linalg.norm(eye)))
     bg = tuple(rng.uniform(0, 0.8, 3))
+    return s, cam, bg
+
+
+def _random_world(rtw, orc, seed, W, H, SPP, max_depth=50):
+    s, cam, bg = mixed_world(rtw, seed, W, H)
     text, imgs = s.dump(), s.images()
     s.commit()
     g, st = rtw.Raytracer(s, cam, bg, W, H, SPP, seed=seed, max_depth=max_depth).render()
@@ -120,8 +127,24 @@ def test_random_mesh_bit_exact(gpu, orc, seed):
     sphere: the mesh kernels (F_MESHES: triangle-only BVH leaves, half-precision nodes where built, the 16-bit-stack
     walk) on trees nobody tuned."""
     rtw = gpu
+    s, cam, bg = mesh_world(rtw, seed)
+    text, imgs = s.dump(), s.images()
+    s.commit()
+    g, st = rtw.Raytracer(s, cam, bg, W, H, SPP, seed=seed).render()
+    r, rays = orc.OracleScene(text, imgs).render(orc.camera_from_fields(cam.as_dict()), bg, W, H, SPP, seed=seed)
+    assert st["rays"] == rays
+    bad = np.argwhere(g.view(np.uint32) != r.view(np.uint32))
+    assert bad.size == 0, f"{len(bad)} mismatching components, first {bad[:4].tolist()}"
+    assert s.info(3) > 0
+
+
+def mesh_world(rtw, seed, max_triangles=None):
+    """-> (the uncommitted scene of mesh world `seed`, its camera, its background); max_triangles caps the soup for
+    tests/test_ray_corpus.py, whose oracle walks the flat list once per segment"""
     rng = np.random.default_rng(2000 + seed)
     n = int(rng.integers(1500, 6000))
+    if max_triangles is not None:
+        n = min(n, max_triangles)
     s = rtw.Scene()
     white = s.lambertian_solid((0.73, 0.73, 0.73))
     img = s.lambertian(s.image(rng.integers(0, 256, (16, 16, 3), dtype=np.uint8)))
@@ -135,11 +158,4 @@ def test_random_mesh_bit_exact(gpu, orc, seed):
     s.sphere((0, -1000, 0), 995, ground)
     cam = rtw.Camera.new((float(rng.uniform(-8, 8)), 2.0, 9.0), (0, 0, 0), (0, 1, 0), 45.0, W / H, 0.0, 9.0)
     bg = (0.1, 0.1, 0.15)
-    text, imgs = s.dump(), s.images()
-    s.commit()
-    g, st = rtw.Raytracer(s, cam, bg, W, H, SPP, seed=seed).render()
-    r, rays = orc.OracleScene(text, imgs).render(orc.camera_from_fields(cam.as_dict()), bg, W, H, SPP, seed=seed)
-    assert st["rays"] == rays
-    bad = np.argwhere(g.view(np.uint32) != r.view(np.uint32))
-    assert bad.size == 0, f"{len(bad)} mismatching components, first {bad[:4].tolist()}"
-    assert s.info(3) > 0
+    return s, cam, bg

@@ -1,12 +1,15 @@
 """Radiance queries on the GPU (rtw_sample_rays*: Raytracer::sample_ray, lib.rs:97-117, for rays the caller chooses,
 every path traced to its end in one persistent launch of the scene's own path-kernel variant).
 
-Every comparison is bit for bit, on uint32 views.  Two references, each computed once per world and shared:
+Every comparison is bit for bit, on uint32 views.  Three references, each computed once per world and shared:
   * the oracle's render of a frame: the records of the frame's camera rays, summed per pixel in sample order in
     float32, are its image, and the sum of their `segments` its ray count;
   * the composed loop written here, camera_rays -> (hit_rays -> scatter_rays)* per path over the host queries, which
     gives every path's colour, segment count, final stream word and end kind: for camera rays and for rays no camera
     made (origins inside the worlds, random directions, times and stream words).
+  * for the rays no camera made, the oracle's own sample_ray on them as well (oracle_sample_rays, which
+    tests/test_ray_corpus.py ties to the oracle's render): the composed loop runs the kernels' shared bodies, so it moves
+    with them; tests/test_gpu_ray_corpus.py holds all three queries to the oracle on a corpus of such rays.
 The composed loop's records do not depend on the walk (tests/test_gpu_hit_rays.py pins hit_rays in every walk), so the
 knob cases compare the fused kernel of each variant against the records made once under the default knobs."""
 import functools
@@ -137,14 +140,25 @@ def _stray(rtw, name, max_depth):
 
 
 @functools.lru_cache(maxsize=None)
+def _stray_oracle(rtw, orc, name, max_depth):
+    """oracle_sample_rays (sample_ray_iter on the flat list, tests/test_ray_corpus.py) on the stray rays: the reference
+    that shares no code with the kernels"""
+    _s, _cam, bg, text, imgs = _world(rtw, name, 16 / 9 if name == "jumpy-balls" else 1.0)
+    rec = orc.OracleScene(text, imgs).sample_rays(_stray(rtw, name, max_depth)[0], bg, max_depth)
+    rec.setflags(write=False)
+    return rec
+
+
+@functools.lru_cache(maxsize=None)
 def _material_world(rtw):
     """Five spheres, one per material, one Metal with fuzz 1 (it absorbs grazing rays): 120 rays aimed at each from
-    all around, a list-mode world of every material kind -> (scene, background, rays, fused, composed, kinds)."""
+    all around, a list-mode world of every material kind -> (scene, background, rays, fused, composed, kinds, dump)."""
     s = rtw.Scene()
     ids = [s.lambertian_solid((0.8, 0.3, 0.1)), s.metal((0.9, 0.8, 0.7), 1.0), s.metal((0.6, 0.7, 0.8), 0.3),
            s.dielectric(1.5), s.diffuse_light(s.solid_rgb(4.0, 3.0, 2.0))]
     for k, m in enumerate(ids):
         s.sphere((3.0 * k, 0.0, 0.0), 1.0, m)
+    text = s.dump()
     s.commit(device=0)
     rng = np.random.default_rng(21)
     n = 600
@@ -168,7 +182,7 @@ def _material_world(rtw):
     bg = (0.25, 0.5, 0.75)
     got = s.sample_rays(rays, bg, 50, device=0)
     want, kind = _compose(rtw, s, rays, bg, 50)
-    return s, bg, rays, got, want, kind
+    return s, bg, rays, got, want, kind, text
 
 
 # ---------------------------------------------------------------- 1. against the oracle's render
@@ -206,18 +220,20 @@ def test_camera_ray_samples_equal_the_composed_loop(gpu, orc, frame):
 
 
 @pytest.mark.parametrize("name,max_depth", [("jumpy-balls", 50), ("cornell-box", 3), ("cornell-box", 50)])
-def test_stray_ray_samples_equal_the_composed_loop(gpu, name, max_depth):
+def test_stray_ray_samples_equal_the_composed_loop(gpu, orc, name, max_depth):
     rays, got, st, want, kind = _stray(gpu, name, max_depth)
     assert len(rays) == 2000 and (kind >= 0).all()
     _same_records(got, want, f"{name} at depth {max_depth}")
+    _same_records(got, _stray_oracle(gpu, orc, name, max_depth), f"{name} at depth {max_depth}, against the oracle")
     assert st["rays"] == int(want["segments"].sum()) and st["paths"] == 2000
     assert (want["segments"] <= max_depth).all() and (want["segments"] >= 1).all()
 
 
-def test_material_world_samples_equal_the_composed_loop(gpu):
-    s, _bg, _rays, got, want, kind = _material_world(gpu)
+def test_material_world_samples_equal_the_composed_loop(gpu, orc):
+    s, bg, rays, got, want, kind, text = _material_world(gpu)
     assert s.info(3) == 0 and s.info(19) == (((1 << 16) - 1) | (1 << 17)) | (1 << 16), "the all-features list kernel"
     _same_records(got, want, "one sphere per material")
+    _same_records(got, orc.OracleScene(text).sample_rays(rays, bg, 50), "one sphere per material, against the oracle")
     assert (kind == ABSORBED).sum() >= 10, "the fuzz-1 Metal absorbs"
 
 
@@ -229,6 +245,10 @@ def test_every_end_kind_occurs(gpu, orc):
     count = np.bincount(np.concatenate(kinds), minlength=4)
     assert (count >= 10).all(), dict(zip(("miss", "light", "absorbed", "depth"), count.tolist()))
     assert np.bincount(_stray(gpu, "cornell-box", 3)[4], minlength=4)[DEPTH] >= 100
+    # the stray paths' ends in the oracle's account: a miss, no scatter (a light, an absorbed ray), depth
+    ends = np.array([gpu.SAMPLE_END_MISS, gpu.SAMPLE_END_NO_SCATTER, gpu.SAMPLE_END_NO_SCATTER, gpu.SAMPLE_END_DEPTH])
+    for name, max_depth in (("jumpy-balls", 50), ("cornell-box", 3), ("cornell-box", 50)):
+        assert (_stray_oracle(gpu, orc, name, max_depth)["flags"] == ends[_stray(gpu, name, max_depth)[4]]).all()
 
 
 # ---------------------------------------------------------------- 3. regeneration and every walk
