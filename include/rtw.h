@@ -73,7 +73,11 @@ typedef struct {
   uint64_t sub_cycles[4];
 } rtw_stats;
 
-enum { RTW_FLAG_COUNT_TRAVERSAL = 1 };
+enum {
+  RTW_FLAG_COUNT_TRAVERSAL = 1,
+  /* rtw_render_samples_device with d_tile_ids: d_sum and d_sq are full w x h x 3 images, each named tile at its place */
+  RTW_FLAG_FULL_IMAGE = 2
+};
 
 const char* rtw_last_error(void);
 int rtw_abi_version(void);
@@ -284,6 +288,50 @@ int rtw_render_progressive(rtw_scene* s, const rtw_camera* cam, const float back
  * spp = 0. */
 int rtw_tonemap_device(int device, const float* d_rgb_sum, uint32_t n_pixels, uint32_t spp, uint8_t* d_rgb8,
                        void* stream);
+
+/* ---- adaptive sampling: the sample count follows a per-tile noise estimate made from the two sums above.  A tile
+ *      that stopped at n samples holds exactly rtw_render's pixels of an n-spp frame (same seed), since samples are
+ *      only ever added in order: every parity guarantee of the fixed-spp frame carries over tile by tile.
+ *      The estimate of an 8x8 tile whose pixels hold n samples, all in f32, one rounding per operation, inv = 1.0f / n:
+ *      per in-image pixel and channel c  m_c = s_c inv,  v_c = max0(q_c inv - m_c m_c)  (a NaN stays a NaN);
+ *      e = (v_0 + v_1) + v_2, l = (m_0 + m_1) + m_2, and +0 for the pixels of a ragged tile that are off the image;
+ *      E, L = the sums of the tile's 64 e and l (pixel (x, y) of the tile at index 8 y + x) by the adjacent-pair tree
+ *      (level k = 0..5: x[i] = x[i] + x[i ^ (1 << k)]);  Pf = the tile's in-image pixels;
+ *      err = sqrt((E inv) / Pf) / (|L| / Pf + 0.03).   The tile is converged iff err <= threshold (a NaN never is). */
+/* The estimate of n_in tiles of the DEVICE images d_sum / d_sq (full w x h x 3 layout, `samples` >= 1 samples in every
+ * tested pixel), on `stream`; only enqueues.  d_ids_in: device tile ids, NULL = the tiles 0 .. n_in - 1 (n_in = the
+ * tile count: every tile); an id beyond the last tile is skipped.  d_err[tile] = err and, unless NULL,
+ * d_tile_samples[tile] = samples, both by global tile id and for tested tiles only.  d_ids_out receives the ids of the
+ * tiles NOT converged, in input order (an ascending list stays ascending), *d_n_out their number; d_ids_out needs room
+ * for n_in ids, serves as the call's scratch and must not overlap d_ids_in.  device < 0: the current device.
+ * RTW_EINVAL: a NULL buffer (d_ids_in and d_tile_samples excepted), an image under 2x2 or over 65536 a side,
+ * samples == 0, a threshold that is NaN, negative or infinite. */
+int rtw_tile_noise_device(int device, const float* d_sum, const float* d_sq, uint32_t w, uint32_t h,
+                          const uint32_t* d_ids_in, uint32_t n_in, uint32_t samples, float threshold, float* d_err,
+                          uint32_t* d_tile_samples, uint32_t* d_ids_out, uint32_t* d_n_out, void* stream);
+/* A fresh frame (d_sum and d_sq, full w x h x 3 device images, are zeroed first) whose tiles stop when converged.
+ * Rounds end at n_0 = min_spp, n_{k+1} = min(2 n_k, max_spp) samples per pixel: each adds the missing samples to the
+ * tiles still active (rtw_render_samples_device with their ids and RTW_FLAG_FULL_IMAGE), then tests them as above; the
+ * tiles not converged go on, until max_spp.  d_tile_samples[tiles]: the samples each tile holds; d_tile_err[tiles] (may
+ * be NULL): its last estimate.  Blocking on `stream`: one 4-byte count is read back per round.  Checks in the render
+ * calls' order: a NULL argument (d_sq and d_tile_samples included), the scene's state, an image under 2x2, then
+ * 2 <= min_spp <= max_spp <= 2^31 and the threshold as above (RTW_EINVAL), then the device copy (RTW_ENODEV).
+ * max_depth = 0 leaves zeros, every tile converged at min_spp.  flags: RTW_FLAG_COUNT_TRAVERSAL.  stats: rays and
+ * kernel_ms summed over the rounds (the tests' kernels included), paths = 64 x the sum of d_tile_samples.  Serialised
+ * with the (scene, device) pair's other renders, as rtw_render_samples_device. */
+int rtw_render_adaptive_device(rtw_scene* s, int device, const rtw_camera* cam, const float background[3],
+                               uint32_t w, uint32_t h, uint32_t min_spp, uint32_t max_spp, uint32_t max_depth,
+                               uint64_t seed, float threshold, float* d_sum, float* d_sq, uint32_t* d_tile_samples,
+                               float* d_tile_err, void* stream, uint32_t flags, rtw_stats* stats);
+/* The host form, on the first device copy: rgb_sum[w*h*3], rgb_sq_sum[w*h*3] (may be NULL), tile_samples[tiles],
+ * tile_err[tiles] (may be NULL) are host arrays.  The device images live in buffers the device copy keeps. */
+int rtw_render_adaptive(rtw_scene* s, const rtw_camera* cam, const float background[3], uint32_t w, uint32_t h,
+                        uint32_t min_spp, uint32_t max_spp, uint32_t max_depth, uint64_t seed, float threshold,
+                        float* rgb_sum, float* rgb_sq_sum, uint32_t* tile_samples, float* tile_err, rtw_stats* stats);
+/* rtw_tonemap_tiles (below) from DEVICE arrays to a DEVICE RGB8 image on `stream`, byte for byte; only enqueues.
+ * device < 0: the current device.  RTW_EINVAL: a NULL buffer, an image under 2x2 or over 65536 a side. */
+int rtw_tonemap_tiles_device(int device, const float* d_rgb_sum, uint32_t w, uint32_t h,
+                             const uint32_t* d_tile_samples, uint8_t* d_rgb8, void* stream);
 
 /* ---- closest-hit ray queries: Hittable::hit(&ray, t_min, t_max) -> Option<HitRecord> on the world list
  *      (hittable/mod.rs:22-69) for rays the caller chooses.  A query is world.hit(ray, 0.001, +inf), the interval of
@@ -505,6 +553,10 @@ int rtw_diag_tile_beam(const rtw_camera* cam, uint32_t w, uint32_t h, uint32_t t
 
 /* console_app/src/main.rs:68-90 tonemap: sqrt(sum/spp), clamp [0, 0.999], u8(255.999*c). */
 int rtw_tonemap(const float* rgb_sum, uint32_t n_pixels, uint32_t spp, uint8_t* rgb8);
+/* rtw_tonemap of an adaptive frame: every pixel of 8x8 tile t (row-major tiles, ragged edges whole) with
+ * spp = tile_samples[t], byte for byte rtw_tonemap of that tile at that spp; a tile with 0 samples is black.
+ * RTW_EINVAL: a NULL buffer, an image under 2x2 or over 65536 a side. */
+int rtw_tonemap_tiles(const float* rgb_sum, uint32_t w, uint32_t h, const uint32_t* tile_samples, uint8_t* rgb8);
 
 /* ---- scene presets: console_app/src/scenes.rs restated (jumpy-balls :63-162, two-spheres
  *      :164-209, two-perlin-spheres :211-252, earth :254-288, simple-light :290-348, cornell-box

@@ -32,6 +32,7 @@ MODELS_DIR = REPO_ROOT / "models"
 
 RTW_EINVAL, RTW_ENOMEM, RTW_ENODEV, RTW_ESTATE, RTW_EIO = -22, -12, -19, -71, -5
 FLAG_COUNT_TRAVERSAL = 1
+FLAG_FULL_IMAGE = 2  # render_samples_device with tile ids: full-layout sums
 NO_MATERIAL = 0xFFFFFFFF
 
 
@@ -166,6 +167,18 @@ _SIGS = {
                                          C.c_uint32, C.c_uint64, C.c_uint32, FRAME_SINK, C.c_void_p,
                                          C.POINTER(rtw_stats)]),
     "rtw_tonemap_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rtw_tile_noise_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
+                                        C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+    "rtw_render_adaptive_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(rtw_camera), _F, C.c_uint32, C.c_uint32,
+                                             C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_float, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                             C.POINTER(rtw_stats)]),
+    "rtw_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(rtw_camera), _F, C.c_uint32, C.c_uint32, C.c_uint32,
+                                      C.c_uint32, C.c_uint32, C.c_uint64, C.c_float, _F, _F, _U32, _F,
+                                      C.POINTER(rtw_stats)]),
+    "rtw_tonemap_tiles_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
     "rtw_hit_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(rtw_ray), C.POINTER(rtw_hit),
                                C.POINTER(rtw_stats)]),
     "rtw_hit_rays_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -199,6 +212,7 @@ _SIGS = {
     "rtw_unpack_tiles_device": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtw_tonemap": (C.c_int, [_F, C.c_uint32, C.c_uint32, _U8]),
+    "rtw_tonemap_tiles": (C.c_int, [_F, C.c_uint32, C.c_uint32, _U32, _U8]),
     "rtw_diag_libm": (C.c_int, [C.c_int, C.c_uint32, _F, _F, _F]),
     "rtw_diag_recip": (C.c_int, [C.c_uint32, _F, _F]),
     "rtw_diag_tile_lists": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(rtw_camera), C.c_uint32, C.c_uint32, _U32,
@@ -736,6 +750,67 @@ class Raytracer:
         if rc < 0:
             _check(rc)
         return rc, st.as_dict()
+
+
+    def render_adaptive(self, threshold: float, min_spp: int = 16, want_sq: bool = False):
+        """The frame with a sample count per 8x8 tile (rtw_render_adaptive; the constructor's spp is the maximum): rounds
+        end at min_spp, 2 min_spp, ... samples, and a tile stops once its noise estimate is <= threshold.  A tile that
+        stopped at n samples holds render()'s pixels of an n-spp frame.  -> (sums[h, w, 3], tile_samples[tiles],
+        tile_err[tiles], stats), with the sums of squares[h, w, 3] after the sums when want_sq."""
+        out = np.empty((self.h, self.w, 3), np.float32)
+        sq = np.empty((self.h, self.w, 3), np.float32) if want_sq else None
+        nt = n_tiles(self.w, self.h)
+        ts, err = np.zeros(nt, np.uint32), np.zeros(nt, np.float32)
+        st = rtw_stats()
+        _check(lib().rtw_render_adaptive(self.scene._p, C.byref(self.cam.c), _fp(self.bg), self.w, self.h, min_spp,
+                                         self.spp, self.max_depth, self.seed, threshold, _fp(out),
+                                         _fp(sq) if want_sq else None, _up(ts), _fp(err), C.byref(st)))
+        return (out, sq, ts, err, st.as_dict()) if want_sq else (out, ts, err, st.as_dict())
+
+    def render_adaptive_device(self, threshold: float, d_sum_ptr: int, d_sq_ptr: int, d_tile_samples_ptr: int,
+                               d_tile_err_ptr: int = 0, min_spp: int = 16, device: int = 0, stream_ptr: int = 0,
+                               flags: int = 0, want_stats: bool = False):
+        """render_adaptive into device memory (rtw_render_adaptive_device; blocking on the stream): full-layout sums and
+        sums of squares (zeroed by the call), tile_samples[tiles] (uint32) and, unless 0, tile_err[tiles] (float32)."""
+        st = rtw_stats()
+        _check(lib().rtw_render_adaptive_device(
+            self.scene._p, device, C.byref(self.cam.c), _fp(self.bg), self.w, self.h, min_spp, self.spp, self.max_depth,
+            self.seed, threshold, C.c_void_p(d_sum_ptr), C.c_void_p(d_sq_ptr), C.c_void_p(d_tile_samples_ptr),
+            C.c_void_p(d_tile_err_ptr) if d_tile_err_ptr else None, C.c_void_p(stream_ptr), flags,
+            C.byref(st) if want_stats else None))
+        return st.as_dict() if want_stats else None
+
+
+def tile_noise_device(d_sum_ptr: int, d_sq_ptr: int, w: int, h: int, samples: int, threshold: float, d_err_ptr: int,
+                      d_ids_out_ptr: int, d_n_out_ptr: int, d_ids_in_ptr: int = 0, n_in=None,
+                      d_tile_samples_ptr: int = 0, device: int = -1, stream_ptr: int = 0):
+    """rtw_tile_noise_device: enqueue the per-tile noise estimate of full-layout device sums holding `samples` samples
+    per pixel; d_ids_in_ptr = 0 tests every tile.  err (and tile_samples, unless 0) by global tile id; the ids of the
+    tiles above the threshold, in input order, to d_ids_out (room for n_in ids) and their number to d_n_out."""
+    n = n_tiles(w, h) if n_in is None else n_in
+    _check(lib().rtw_tile_noise_device(device, C.c_void_p(d_sum_ptr), C.c_void_p(d_sq_ptr), w, h,
+                                       C.c_void_p(d_ids_in_ptr) if d_ids_in_ptr else None, n, samples, threshold,
+                                       C.c_void_p(d_err_ptr), C.c_void_p(d_tile_samples_ptr) if d_tile_samples_ptr else None,
+                                       C.c_void_p(d_ids_out_ptr), C.c_void_p(d_n_out_ptr), C.c_void_p(stream_ptr)))
+
+
+def tonemap_tiles(sums: np.ndarray, tile_samples) -> np.ndarray:
+    """rtw_tonemap_tiles: tonemap() of sums[h, w, 3] with a sample count per 8x8 tile (0 = black) -> uint8[h, w, 3]."""
+    s = np.ascontiguousarray(sums, np.float32)
+    h, w = s.shape[:2]
+    ts = _ua(tile_samples)
+    if ts.size != n_tiles(w, h):
+        raise ValueError(f"tile_samples has {ts.size} entries, the {w}x{h} image {n_tiles(w, h)} tiles")
+    out = np.empty(s.shape, np.uint8)
+    _check(lib().rtw_tonemap_tiles(_fp(s.reshape(-1)), w, h, _up(ts), out.ctypes.data_as(_U8)))
+    return out
+
+
+def tonemap_tiles_device(d_sum_ptr: int, w: int, h: int, d_tile_samples_ptr: int, d_rgb8_ptr: int, device: int = -1,
+                         stream_ptr: int = 0):
+    """tonemap_tiles() over device arrays, enqueued on a stream."""
+    _check(lib().rtw_tonemap_tiles_device(device, C.c_void_p(d_sum_ptr), w, h, C.c_void_p(d_tile_samples_ptr),
+                                          C.c_void_p(d_rgb8_ptr), C.c_void_p(stream_ptr)))
 
 
 def sample_blocks(sample_first: int, n_samples: int) -> list:

@@ -17,6 +17,7 @@
 //   rec.material.scatter(&ray, &rec, rng) / emitted()   world.scatter_rays(rays, hits, background) -> {rays, Scatter}  material.rs:23-26
 //   raytracer.sample_ray(&ray, rng, depth) -> Color      world.sample_rays(rays, background, max_depth) -> std::vector<Sample>  lib.rs:97-117
 //   (no counterpart: the frame in growing steps)        Raytracer(..).render_progressive(on_frame, step); sample_blocks; tonemap_device
+//   (no counterpart: a sample count per 8x8 tile)       Raytracer(..).render_adaptive(threshold, min_spp) -> AdaptiveFrame; tile_noise_device; tonemap_tiles
 // Errors (the reference panics) throw rtw::Error with rtw_last_error()'s message.
 #pragma once
 #include <stdexcept>
@@ -231,6 +232,14 @@ class World {
   rtw_scene* s_ = nullptr;
 };
 
+// Raytracer::render_adaptive's frame: flat RGB sums in render_sums' layout, and per 8x8 tile (row-major, ragged edges
+// whole) the samples its pixels hold and its last noise estimate
+struct AdaptiveFrame {
+  std::vector<float> sums;
+  std::vector<uint32_t> tile_samples;
+  std::vector<float> tile_err;
+};
+
 // lib.rs:40-95
 class Raytracer {
  public:
@@ -280,6 +289,26 @@ class Raytracer {
     check(rtw_render_samples_device(world_.raw(), device, &cam_.c, bg, w_, h_, first, n, depth_, seed_, d_tile_ids,
                                     n_tiles, d_sum, d_sq, stream, flags, st));
   }
+  // The frame with a sample count per tile (rtw_render_adaptive; the constructor's spp is the maximum): a tile stops at
+  // the first of min_spp, 2 min_spp, ... samples at which its noise estimate is <= threshold, and then holds
+  // render_sums' pixels of a frame of that many samples.
+  AdaptiveFrame render_adaptive(float threshold, uint32_t min_spp = 16, rtw_stats* st = nullptr) const {
+    const size_t tiles = (size_t)((w_ + 7u) / 8u) * ((h_ + 7u) / 8u);
+    AdaptiveFrame f{std::vector<float>((size_t)w_ * h_ * 3), std::vector<uint32_t>(tiles), std::vector<float>(tiles)};
+    const float bg[3] = {bg_.x, bg_.y, bg_.z};
+    check(rtw_render_adaptive(world_.raw(), &cam_.c, bg, w_, h_, min_spp, spp_, depth_, seed_, threshold, f.sums.data(),
+                              nullptr, f.tile_samples.data(), f.tile_err.data(), st));
+    return f;
+  }
+  // The same into device memory (rtw_render_adaptive_device; blocking on `stream`): full-layout d_sum and d_sq, zeroed
+  // by the call, d_tile_samples[tiles] and d_tile_err[tiles] (or nullptr)
+  void render_adaptive_device(int device, float threshold, uint32_t min_spp, float* d_sum, float* d_sq,
+                              uint32_t* d_tile_samples, float* d_tile_err = nullptr, void* stream = nullptr,
+                              uint32_t flags = 0, rtw_stats* st = nullptr) const {
+    const float bg[3] = {bg_.x, bg_.y, bg_.z};
+    check(rtw_render_adaptive_device(world_.raw(), device, &cam_.c, bg, w_, h_, min_spp, spp_, depth_, seed_, threshold,
+                                     d_sum, d_sq, d_tile_samples, d_tile_err, stream, flags, st));
+  }
 
  private:
   World& world_;
@@ -302,6 +331,26 @@ inline std::vector<std::pair<uint32_t, uint32_t>> sample_blocks(uint32_t first, 
 inline void tonemap_device(const float* d_rgb_sum, uint32_t n_pixels, uint32_t spp, uint8_t* d_rgb8, int device = -1,
                            void* stream = nullptr) {
   check(rtw_tonemap_device(device, d_rgb_sum, n_pixels, spp, d_rgb8, stream));
+}
+// The per-tile noise estimate of full-layout device sums holding `samples` samples per pixel, enqueued on `stream`
+// (rtw_tile_noise_device): d_err (and d_tile_samples, or nullptr) by global tile id, the ids of the tiles above the
+// threshold in input order to d_ids_out, their number to *d_n_out; d_ids_in = nullptr tests tiles 0 .. n_in - 1
+inline void tile_noise_device(const float* d_sum, const float* d_sq, uint32_t w, uint32_t h, const uint32_t* d_ids_in,
+                              uint32_t n_in, uint32_t samples, float threshold, float* d_err, uint32_t* d_tile_samples,
+                              uint32_t* d_ids_out, uint32_t* d_n_out, int device = -1, void* stream = nullptr) {
+  check(rtw_tile_noise_device(device, d_sum, d_sq, w, h, d_ids_in, n_in, samples, threshold, d_err, d_tile_samples,
+                              d_ids_out, d_n_out, stream));
+}
+// rtw_tonemap with a sample count per 8x8 tile (rtw_tonemap_tiles), and over device arrays (rtw_tonemap_tiles_device)
+inline std::vector<uint8_t> tonemap_tiles(const std::vector<float>& sums, uint32_t w, uint32_t h,
+                                          const std::vector<uint32_t>& tile_samples) {
+  std::vector<uint8_t> out((size_t)w * h * 3);
+  check(rtw_tonemap_tiles(sums.data(), w, h, tile_samples.data(), out.data()));
+  return out;
+}
+inline void tonemap_tiles_device(const float* d_rgb_sum, uint32_t w, uint32_t h, const uint32_t* d_tile_samples,
+                                 uint8_t* d_rgb8, int device = -1, void* stream = nullptr) {
+  check(rtw_tonemap_tiles_device(device, d_rgb_sum, w, h, d_tile_samples, d_rgb8, stream));
 }
 
 }  // namespace rtw

@@ -463,6 +463,21 @@ int rtw_tonemap(const float* sum, uint32_t n, uint32_t spp, uint8_t* out) {
   return RTW_OK;
 }
 
+int rtw_tonemap_tiles(const float* sum, uint32_t w, uint32_t h, const uint32_t* tile_samples, uint8_t* out) {
+  if (!sum || !tile_samples || !out) return fail(RTW_EINVAL, "NULL buffer");
+  if (int e = check_image_min(w, h)) return e;
+  if (int e = check_image_max(w, h)) return e;
+  const uint32_t tiles_x = (w + 7u) / 8u;
+  for (uint32_t row = 0; row < h; ++row)
+    for (uint32_t i = 0; i < w; ++i) {
+      const uint32_t n = tile_samples[(size_t)(row >> 3) * tiles_x + (i >> 3)];
+      const size_t at = ((size_t)row * w + i) * 3;
+      if (n == 0) out[at] = out[at + 1] = out[at + 2] = 0;
+      else if (int e = rtw_tonemap(sum + at, 1, n, out + at)) return e;
+    }
+  return RTW_OK;
+}
+
 // ---------------------------------------------------------------- ProgressMessage wire format
 // postcard 0.7: varint (LEB128) u32 and enum tags, f32 little-endian; then COBS + 0x00.
 static void put_varint(std::vector<uint8_t>& o, uint32_t v) {

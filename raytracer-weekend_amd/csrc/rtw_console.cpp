@@ -1,11 +1,13 @@
 // rtw_console.cpp — the build's console_app (console_app/src/main.rs:15-96) on the GPU core.
 //
 //   rtw_console <scene> [-w|--width 400] [-a|--aspect-ratio 1.7777778] [-s|--samples-per-pixel 100]
-//               [--seed 0] [--models models] [--out render] [--progressive STEP]
+//               [--seed 0] [--models models] [--out render] [--progressive STEP] [--adaptive THRESHOLD [--min-spp 16]]
 // Same Opts and defaults (main.rs:15-26), height = round(width / aspect) (:33), camera
 // aspect = width / height as f32 (:38-41), tonemap (:68-90), PNG to render/image_0000.png (:92-94).
 // --progressive (no counterpart in console_app) renders each frame through rtw_render_progressive: the PNG is rewritten
 // after every step, and its last version is the one-shot frame's file byte for byte.
+// --adaptive renders each frame through rtw_render_adaptive with -s as the most samples a tile gets, and writes the PNG
+// through rtw_tonemap_tiles: every 8x8 tile is the one-shot frame's at the sample count it stopped at.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -13,6 +15,8 @@
 #include <sys/stat.h>
 #include <zlib.h>
 
+#include <algorithm>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -78,8 +82,9 @@ static double mean_rel_stderr(const float* sum, const float* sq, size_t n_pixels
 
 int main(int argc, char** argv) {
   std::string scene, models = "models", out_dir = "render";
-  uint32_t width = 400, spp = 100, step = 0;
-  bool progressive = false;
+  uint32_t width = 400, spp = 100, step = 0, min_spp = 16;
+  bool progressive = false, adaptive = false;
+  float threshold = 0.0f;
   double aspect = 1.7777778;
   uint64_t seed = 0;
   for (int k = 1; k < argc; ++k) {
@@ -95,11 +100,13 @@ int main(int argc, char** argv) {
     else if (a == "--models") models = next("--models");
     else if (a == "--out") out_dir = next("--out");
     else if (a == "--progressive") { progressive = true; step = (uint32_t)atoi(next("--progressive")); }
+    else if (a == "--adaptive") { adaptive = true; threshold = (float)atof(next("--adaptive")); }
+    else if (a == "--min-spp") min_spp = (uint32_t)atoi(next("--min-spp"));
     else if (a == "-h" || a == "--help") {
       printf("usage: rtw_console <jumpy-balls|two-spheres|two-perlin-spheres|earth|simple-light|cornell-box|"
              "smokey-cornell-box|book2-final-scene|animated-book2-final-scene|simple-triangle|wavefront-cow-obj|"
              "wavefront-suspension-obj|textured-monument> [-w W] [-a ASPECT] [-s SPP] [--seed N] [--models DIR] "
-             "[--out DIR] [--progressive STEP]\n"
+             "[--out DIR] [--progressive STEP] [--adaptive THRESHOLD [--min-spp N]]\n"
              "  --progressive STEP  render each frame in growing steps (1, 2, 4, ... samples while the doubled count is\n"
              "      within STEP, then STEP at a time; 0 = doubling to the end); after every step the frame's PNG is\n"
              "      rewritten and the samples done and the mean relative standard error are printed.  That error, from\n"
@@ -107,7 +114,11 @@ int main(int argc, char** argv) {
              "      variance v = max(0, Q / n - m^2) n / (n - 1); the luminance Y = 0.2126 R + 0.7152 G + 0.0722 B has\n"
              "      mean sum_c w_c m_c and standard error sum_c w_c sqrt(v_c / n) (the channels taken as fully\n"
              "      correlated: an upper bound); a pixel's relative error is the second over the first, and the frame's\n"
-             "      is its average over the pixels whose mean luminance is not zero (n/a at n = 1).\n");
+             "      is its average over the pixels whose mean luminance is not zero (n/a at n = 1).\n"
+             "  --adaptive THRESHOLD [--min-spp N]  a sample count per 8x8 tile: every tile gets N (default 16) samples,\n"
+             "      then 2 N, 4 N, ... up to SPP, and stops at the first count at which its noise estimate (rtw.h: the\n"
+             "      tile's root mean variance of the mean over its mean brightness + 0.03) is <= THRESHOLD.  Prints the\n"
+             "      number of tiles per sample count.\n");
       return 0;
     } else if (scene.empty()) scene = a;
     else { fprintf(stderr, "unexpected argument '%s'\n", a.c_str()); return 2; }
@@ -141,6 +152,13 @@ int main(int argc, char** argv) {
           return 0;
         }, step, &st);
         if (rc) { fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
+      } else if (adaptive) {
+        const rtw::AdaptiveFrame fr = rt.render_adaptive(threshold, std::min(min_spp, spp), &st);
+        rtw::check(rtw_tonemap_tiles(fr.sums.data(), width, height, fr.tile_samples.data(), img.data()));
+        if (!write_png(path.c_str(), img.data(), width, height)) { fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
+        std::map<uint32_t, size_t> hist;
+        for (uint32_t n : fr.tile_samples) ++hist[n];
+        for (const auto& kv : hist) printf("  %u spp: %zu tiles\n", kv.first, kv.second);
       } else {
         std::vector<float> sums = rt.render_sums(&st);
         rtw::check(rtw_tonemap(sums.data(), width * height, spp, img.data()));

@@ -1,8 +1,8 @@
 // rtw_kernel.hip — what of the gfx950 path-tracing megakernel's host side needs the device compiler: the kernels
 // that are no templates (reduce_kernel, unpack_tiles_kernel, tile_list_kernel with its diagnostic calls, the libm and
 // reciprocal diagnostics, with the two calls that launch the latter), the tuning knobs, pick_kernel (which path-kernel variant a scene runs) and the launches
-// (enqueue_render, enqueue_render_samples, enqueue_tonemap, enqueue_hit_rays, enqueue_sample_rays, enqueue_scatter_rays,
-// enqueue_camera_rays, enqueue_unpack),
+// (enqueue_render, enqueue_render_samples, enqueue_tonemap, enqueue_tile_noise, enqueue_tonemap_tiles, enqueue_hit_rays,
+// enqueue_sample_rays, enqueue_scatter_rays, enqueue_camera_rays, enqueue_unpack),
 // which share one cache of resident grids (resident_blocks), the walk's tuning (tune_walk) and the one-record-per-lane
 // queries' launch (launch_query).  The
 // scene's device copies, statistics and the render entry points are plain HIP runtime code in rtw_render.cpp, the
@@ -47,6 +47,9 @@
 // Progressive renders (rtw_render_samples_device, rtw_render_progressive): a range of samples runs as aligned
 // power-of-two blocks, each an ordinary round of passes whose key carries the block's base (frame_args), reduced by
 // accumulate_kernel (rtw_film_kernel.hpp) onto the sums the frame holds; tonemap_kernel beside it (rtw_tonemap_device).
+// Adaptive renders (rtw_tile_noise_device, rtw_render_adaptive*): tile_noise_kernel and compact_tiles_kernel of the same
+// header turn the two sums into the ids of the tiles still above the threshold (enqueue_tile_noise); the loop around
+// enqueue_render_samples and it is rtw_render.cpp's.
 // Variants: path_kernel<COUNT, KernelCfg K> -- one plain aggregate (stack rows, spill, waves / SIMD, feature set,
 // workgroup size, LDS node table, half nodes, 16-bit stack) is the template argument, defines every property derived
 // from it, and travels with the kernel to the host (Variant, rtw_variants.hpp), which sizes the launch from it.
@@ -419,7 +422,7 @@ static RenderArgs frame_args(const DeviceCopy& c, const Frame& f, const TileSet&
   a.tile_ids = ts.ids;
   a.tile_first = ts.first;
   a.tile_stride = ts.stride;
-  a.packed_out = (ts.ids || ts.packed) ? 1u : 0u;
+  a.packed_out = ((ts.ids && !ts.full) || ts.packed) ? 1u : 0u;
   a.err = c.err_host;
   // the host mirror of dev::splitmix64 (seed pre-hash shared by every pixel)
   uint64_t z = f.seed + 0x9E3779B97F4A7C15ull;
@@ -740,6 +743,34 @@ int enqueue_tonemap(const float* d_sum, uint32_t n_pixels, uint32_t spp, uint8_t
   const uint32_t grid = (uint32_t)(((uint64_t)n_pixels + dev::FILM_BLOCK - 1u) / dev::FILM_BLOCK);
   hipLaunchKernelGGL(dev::tonemap_kernel, dim3(grid), dim3(dev::FILM_BLOCK), 0, stream, d_sum, n_pixels, scale, d_rgb8);
   HIPCHK(hipGetLastError(), "tonemap_kernel launch");
+  return RTW_OK;
+}
+
+int enqueue_tile_noise(const float* d_sum, const float* d_sq, uint32_t w, uint32_t h, const uint32_t* d_ids_in,
+                       uint32_t n_in, uint32_t samples, float threshold, float* d_err, uint32_t* d_tile_samples,
+                       uint32_t* d_ids_out, uint32_t* d_n_out, hipStream_t stream) {
+  const uint32_t tiles_x = (w + 7u) / 8u, n_tiles = tiles_x * ((h + 7u) / 8u);
+  const float inv = 1.0f / (float)samples;  // one IEEE division, an argument of the kernel
+  if (n_in) {
+    const uint32_t per = dev::FILM_BLOCK / 64u;
+    const uint32_t grid = (uint32_t)(((uint64_t)n_in + per - 1u) / per);
+    hipLaunchKernelGGL(dev::tile_noise_kernel, dim3(grid), dim3(dev::FILM_BLOCK), 0, stream, d_sum, d_sq, w, h, tiles_x,
+                       n_tiles, d_ids_in, n_in, samples, inv, threshold, d_err, d_tile_samples, d_ids_out);
+    HIPCHK(hipGetLastError(), "tile_noise_kernel launch");
+  }
+  hipLaunchKernelGGL(dev::compact_tiles_kernel, dim3(1), dim3(dev::COMPACT_BLOCK), 0, stream, d_ids_in, n_in, d_ids_out,
+                     d_n_out);
+  HIPCHK(hipGetLastError(), "compact_tiles_kernel launch");
+  return RTW_OK;
+}
+
+int enqueue_tonemap_tiles(const float* d_sum, uint32_t w, uint32_t h, const uint32_t* d_tile_samples, uint8_t* d_rgb8,
+                          hipStream_t stream) {
+  const uint64_t n = (uint64_t)w * h;
+  const uint32_t grid = (uint32_t)((n + dev::FILM_BLOCK - 1u) / dev::FILM_BLOCK);
+  hipLaunchKernelGGL(dev::tonemap_tiles_kernel, dim3(grid), dim3(dev::FILM_BLOCK), 0, stream, d_sum, w, h,
+                     (w + 7u) / 8u, d_tile_samples, d_rgb8);
+  HIPCHK(hipGetLastError(), "tonemap_tiles_kernel launch");
   return RTW_OK;
 }
 

@@ -4,7 +4,9 @@
 // of one device.  Plain HIP runtime API: the kernels, which variant a scene runs and how a render is enqueued are
 // rtw_kernel.hip's (enqueue_render, enqueue_render_samples, enqueue_tonemap, enqueue_unpack); the six ray-query calls
 // are rtw_query.cpp's, the render over several devices rtw_multi.cpp's.  The progressive calls
-// (rtw_render_samples_device, rtw_sample_blocks, rtw_render_progressive, rtw_tonemap_device) are here too.
+// (rtw_render_samples_device, rtw_sample_blocks, rtw_render_progressive, rtw_tonemap_device) are here too.  So are the
+// adaptive ones (rtw_tile_noise_device, rtw_render_adaptive_device, rtw_render_adaptive, rtw_tonemap_tiles_device): the
+// loop of rounds around enqueue_render_samples and enqueue_tile_noise is render_adaptive below.
 #include <math.h>
 #include <string.h>
 
@@ -121,8 +123,10 @@ void release(Scene& s) {
     if (c.err_host) hipHostFree(c.err_host);
     if (c.lists_count) hipFree(c.lists_count);
     for (DevBuf* b : {&c.sbuf, &c.spill, &c.image, &c.tiles, &c.packed, &c.gathered, &c.gather_ids, &c.qrays, &c.qhits,
-                       &c.mshade, &c.qscatter, &c.qsamples, &c.pboxes, &c.tile_lists, &c.film_sum, &c.film_sq})
+                       &c.mshade, &c.qscatter, &c.qsamples, &c.pboxes, &c.tile_lists, &c.film_sum, &c.film_sq,
+                       &c.adapt_ids, &c.adapt_tiles})
       free_buf(*b);
+    if (c.adapt_host) hipHostFree(c.adapt_host);
     for (hipEvent_t e : {c.ev[0], c.ev[1], c.gev[0], c.gev[1]})
       if (e) hipEventDestroy(e);
     if (c.stream) hipStreamDestroy(c.stream);
@@ -175,6 +179,13 @@ int check_shutter(const rtw_camera& cam, const Flat& f) {
 static int check_sample_range(uint32_t first, uint32_t n) {
   if ((uint64_t)first + n > (1ull << 31))
     return fail(RTW_EINVAL, "samples [%u, %u + %u) go beyond 2^31", first, first, n);
+  return RTW_OK;
+}
+
+// the adaptive calls' threshold: err <= threshold must be able to hold and to fail
+static int check_threshold(float threshold) {
+  if (!(threshold >= 0.0f) || isinf(threshold))
+    return fail(RTW_EINVAL, "threshold %g: must be finite and >= 0", (double)threshold);
   return RTW_OK;
 }
 
@@ -256,6 +267,70 @@ static int render_device(rtw_scene* s, int device, const Frame& f, const TileSet
   return rc;
 }
 
+// rtw_render_adaptive_device and rtw_render_adaptive behind their checks: c's device is current, the frame's spp is
+// max_spp.  Rounds end at n_0 = min_spp, n_{k+1} = min(2 n_k, max_spp); each adds samples [n_{k-1}, n_k) to the tiles
+// still active (full layout) and tests them; the list of those not converged is the next round's tile set.
+static int render_adaptive(Scene& sc, DeviceCopy& c, const Frame& f, uint32_t min_spp, float threshold, float* d_sum,
+                           float* d_sq, uint32_t* d_tile_samples, float* d_tile_err, hipStream_t stream,
+                           uint32_t flags, rtw_stats* stats) {
+  auto t0 = std::chrono::steady_clock::now();
+  if (int e = check_image_max(f.w, f.h)) return e;
+  const uint32_t nt = (uint32_t)f.tiles();
+  if (int e = copy_events(c)) return e;
+  if (int e = grow(c.adapt_ids, ((size_t)2 * nt + 1) * sizeof(uint32_t))) return e;
+  if (!c.adapt_host)
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c.adapt_host), sizeof(uint32_t), hipHostMallocDefault),
+           "hipHostMalloc(count)");
+  uint32_t* list[2] = {static_cast<uint32_t*>(c.adapt_ids.p), static_cast<uint32_t*>(c.adapt_ids.p) + nt};
+  uint32_t* d_count = list[1] + nt;
+  const size_t bytes = (size_t)f.w * f.h * 3 * sizeof(float);
+  HIPCHK(hipMemsetAsync(d_sum, 0, bytes, stream), "hipMemsetAsync(sums)");
+  HIPCHK(hipMemsetAsync(d_sq, 0, bytes, stream), "hipMemsetAsync(sums of squares)");
+  rtw_stats tot{};
+  const uint32_t* active = nullptr;  // the first round: every tile, no table
+  uint32_t n_active = nt, done = 0;
+  for (uint32_t round = 0; n_active && done < f.spp; ++round) {
+    const uint32_t end = done ? (uint32_t)std::min<uint64_t>(2ull * done, f.spp) : min_spp;
+    Frame chunk = f;
+    chunk.spp = end - done;
+    TileSet ts{active, 0, 1, n_active};
+    ts.full = true;
+    if (int e = enqueue_render_samples(sc, c, chunk, done, ts, d_sum, d_sq, stream, flags, c.ev[0], nullptr)) return e;
+    uint32_t* next = list[round & 1u];
+    if (int e = enqueue_tile_noise(d_sum, d_sq, f.w, f.h, active, n_active, end, threshold, d_tile_err, d_tile_samples,
+                                   next, d_count, stream))
+      return e;
+    HIPCHK(hipEventRecord(c.ev[1], stream), "hipEventRecord");
+    HIPCHK(hipMemcpyAsync(c.adapt_host, d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, stream),
+           "hipMemcpyAsync(count)");
+    rtw_stats st{};
+    if (stats) {
+      if (int e = collect_stats(c, stream, c.ev[0], c.ev[1], 0, &st)) return e;
+    } else {
+      HIPCHK(hipStreamSynchronize(stream), "render_kernel");
+      if (int e = check_guard(c)) return e;
+    }
+    tot.rays += st.rays;
+    tot.kernel_ms += st.kernel_ms;
+    tot.node_visits += st.node_visits;
+    tot.prim_tests += st.prim_tests;
+    tot.paths += (uint64_t)n_active * 64u * (end - done);
+    done = end;
+    active = next;
+    n_active = *static_cast<volatile uint32_t*>(c.adapt_host);
+  }
+  tot.total_ms = ms_since(t0);
+  if (stats) *stats = tot;
+  return RTW_OK;
+}
+
+// the adaptive render calls' checks after check_frame, before the device copy
+static int check_adaptive(uint32_t min_spp, uint32_t max_spp, float threshold) {
+  if (min_spp < 2u || min_spp > max_spp || max_spp > (1u << 31))
+    return fail(RTW_EINVAL, "min_spp %u, max_spp %u: 2 <= min_spp <= max_spp <= 2^31", min_spp, max_spp);
+  return check_threshold(threshold);
+}
+
 }  // namespace rtw
 
 using namespace rtw;
@@ -322,7 +397,8 @@ int rtw_render_samples_device(rtw_scene* s, int device, const rtw_camera* cam, c
   if (int e = check_sample_range(sample_first, n_samples)) return e;
   DeviceCopy* c = need_copy(s->s, device);
   if (!c) return RTW_ENODEV;
-  const TileSet ts{d_tiles, 0, 1, d_tiles ? n_tiles : (uint32_t)f.tiles()};
+  TileSet ts{d_tiles, 0, 1, d_tiles ? n_tiles : (uint32_t)f.tiles()};
+  ts.full = (flags & RTW_FLAG_FULL_IMAGE) != 0;
   DeviceGuard g;
   HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
   if (stats)
@@ -413,6 +489,78 @@ int rtw_tonemap_device(int device, const float* d_rgb_sum, uint32_t n_pixels, ui
   DeviceGuard g;
   if (device >= 0) HIPCHK(hipSetDevice(device), "hipSetDevice");
   return enqueue_tonemap(d_rgb_sum, n_pixels, spp, d_rgb8, abi_stream(stream));
+}
+
+int rtw_tile_noise_device(int device, const float* d_sum, const float* d_sq, uint32_t w, uint32_t h,
+                          const uint32_t* d_ids_in, uint32_t n_in, uint32_t samples, float threshold, float* d_err,
+                          uint32_t* d_tile_samples, uint32_t* d_ids_out, uint32_t* d_n_out, void* stream) {
+  if (!d_sum || !d_sq || !d_err || !d_ids_out || !d_n_out) return fail(RTW_EINVAL, "NULL buffer");
+  if (int e = check_image_min(w, h)) return e;
+  if (int e = check_image_max(w, h)) return e;
+  if (samples == 0) return fail(RTW_EINVAL, "samples must be > 0");
+  if (int e = check_threshold(threshold)) return e;
+  DeviceGuard g;
+  if (device >= 0) HIPCHK(hipSetDevice(device), "hipSetDevice");
+  return enqueue_tile_noise(d_sum, d_sq, w, h, d_ids_in, n_in, samples, threshold, d_err, d_tile_samples, d_ids_out,
+                            d_n_out, abi_stream(stream));
+}
+
+int rtw_render_adaptive_device(rtw_scene* s, int device, const rtw_camera* cam, const float bg[3], uint32_t w,
+                               uint32_t h, uint32_t min_spp, uint32_t max_spp, uint32_t max_depth, uint64_t seed,
+                               float threshold, float* d_sum, float* d_sq, uint32_t* d_tile_samples, float* d_tile_err,
+                               void* stream, uint32_t flags, rtw_stats* stats) {
+  const Frame f{cam, bg, w, h, max_spp, max_depth, seed};
+  if (int e = check_frame(s, f, d_sum && d_sq && d_tile_samples, true)) return e;
+  if (int e = check_adaptive(min_spp, max_spp, threshold)) return e;
+  DeviceCopy* c = need_copy(s->s, device);
+  if (!c) return RTW_ENODEV;
+  DeviceGuard g;
+  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
+  return render_adaptive(s->s, *c, f, min_spp, threshold, d_sum, d_sq, d_tile_samples, d_tile_err, abi_stream(stream),
+                         flags, stats);
+}
+
+int rtw_render_adaptive(rtw_scene* s, const rtw_camera* cam, const float bg[3], uint32_t w, uint32_t h,
+                        uint32_t min_spp, uint32_t max_spp, uint32_t max_depth, uint64_t seed, float threshold,
+                        float* rgb_sum, float* rgb_sq_sum, uint32_t* tile_samples, float* tile_err, rtw_stats* stats) {
+  auto t0 = std::chrono::steady_clock::now();
+  const Frame f{cam, bg, w, h, max_spp, max_depth, seed};
+  if (int e = check_frame(s, f, rgb_sum && tile_samples, true)) return e;
+  if (int e = check_adaptive(min_spp, max_spp, threshold)) return e;
+  DeviceCopy* c = need_copy(s->s, -1, nullptr);
+  if (!c) return RTW_ENODEV;
+  if (int e = check_image_max(w, h)) return e;
+  DeviceGuard g;
+  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
+  const size_t bytes = (size_t)w * h * 3 * sizeof(float), nt = (size_t)f.tiles();
+  if (int e = grow(c->film_sum, bytes)) return e;  // kept for the next frame, as rtw_render_progressive's
+  if (int e = grow(c->film_sq, bytes)) return e;
+  if (int e = grow(c->adapt_tiles, nt * (sizeof(uint32_t) + sizeof(float)))) return e;
+  float* d_sum = static_cast<float*>(c->film_sum.p);
+  float* d_sq = static_cast<float*>(c->film_sq.p);
+  uint32_t* d_ts = static_cast<uint32_t*>(c->adapt_tiles.p);
+  float* d_err = reinterpret_cast<float*>(d_ts + nt);
+  rtw_stats st{};
+  int rc = render_adaptive(s->s, *c, f, min_spp, threshold, d_sum, d_sq, d_ts, d_err, nullptr, 0, &st);
+  if (rc == RTW_OK &&
+      (hipMemcpy(rgb_sum, d_sum, bytes, hipMemcpyDeviceToHost) != hipSuccess ||
+       (rgb_sq_sum && hipMemcpy(rgb_sq_sum, d_sq, bytes, hipMemcpyDeviceToHost) != hipSuccess) ||
+       hipMemcpy(tile_samples, d_ts, nt * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess ||
+       (tile_err && hipMemcpy(tile_err, d_err, nt * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)))
+    rc = fail(RTW_ENODEV, "hipMemcpy(adaptive frame)");
+  st.total_ms = ms_since(t0);
+  if (stats) *stats = st;
+  return rc;
+}
+
+int rtw_tonemap_tiles_device(int device, const float* d_rgb_sum, uint32_t w, uint32_t h,
+                             const uint32_t* d_tile_samples, uint8_t* d_rgb8, void* stream) {
+  if (!d_rgb_sum || !d_tile_samples || !d_rgb8) return fail(RTW_EINVAL, "NULL buffer");
+  if (int e = check_image_min(w, h)) return e;
+  if (int e = check_image_max(w, h)) return e;
+  DeviceGuard g;
+  if (device >= 0) HIPCHK(hipSetDevice(device), "hipSetDevice");
+  return enqueue_tonemap_tiles(d_rgb_sum, w, h, d_tile_samples, d_rgb8, abi_stream(stream));
 }
 
 int rtw_render_status(rtw_scene* s, int device) {

@@ -124,6 +124,10 @@ struct DeviceCopy {
   // 30-camera animation through rtw_render does no hipMalloc after the first frame
   DevBuf image, tiles, packed, gathered, gather_ids;
   DevBuf film_sum, film_sq;                // rtw_render_progressive's device sums: the frame's Σ x and Σ x^2
+  // rtw_render_adaptive*: two tile-id lists of the frame's tile count and the count word behind them (grown once),
+  // the pinned host word the count is read back into, and the host form's per-tile counts and errors
+  DevBuf adapt_ids, adapt_tiles;
+  uint32_t* adapt_host = nullptr;
   DevBuf qrays, qhits;                     // rtw_hit_rays' staging: one chunk of rays and of records
   DevBuf mshade;                           // Flat::mshade (uploaded with the scene; scatter_kernel's material table)
   DevBuf qscatter;                         // rtw_scatter_rays' staging: one chunk of rtw_scatter records
@@ -210,12 +214,13 @@ struct Frame {
   uint64_t paths() const { return (uint64_t)w * h * spp; }
 };
 // Which 8x8 tiles a render covers and where they go: slot k renders tile ids[k] (a device array), or
-// tile first + k * stride without one; the output is packed [slot][64][3] when `packed` (always with
-// ids), else the full w x h image.
+// tile first + k * stride without one; the output is packed [slot][64][3] when `packed`, and with
+// ids unless `full` (RTW_FLAG_FULL_IMAGE: ids, each tile at its place), else the full w x h image.
 struct TileSet {
   const uint32_t* ids = nullptr;
   uint32_t first = 0, stride = 1, n = 0;
   bool packed = false;
+  bool full = false;
 };
 
 // rtw_flatten.cpp
@@ -271,6 +276,17 @@ int enqueue_render_samples(Scene& s, DeviceCopy& c, const Frame& f, uint32_t sam
                            hipEvent_t ev1);
 // enqueue rtw_tonemap over device arrays (n_pixels x rgb sums -> n_pixels x rgb8) on `stream` of the current device
 int enqueue_tonemap(const float* d_sum, uint32_t n_pixels, uint32_t spp, uint8_t* d_rgb8, hipStream_t stream);
+// enqueue the noise test of n_in tiles (d_ids_in, or NULL: tiles 0 .. n_in - 1) of the full-layout sums d_sum / d_sq
+// holding `samples` samples per pixel, on `stream` of the current device: tile_noise_kernel (d_err and d_tile_samples by
+// global tile id, either may be NULL), then the stable compaction of the ids not converged into d_ids_out (room for
+// n_in words, the call's scratch too; it may not overlap d_ids_in) with their number in *d_n_out.  The caller has
+// checked the arguments (rtw_tile_noise_device).
+int enqueue_tile_noise(const float* d_sum, const float* d_sq, uint32_t w, uint32_t h, const uint32_t* d_ids_in,
+                       uint32_t n_in, uint32_t samples, float threshold, float* d_err, uint32_t* d_tile_samples,
+                       uint32_t* d_ids_out, uint32_t* d_n_out, hipStream_t stream);
+// enqueue rtw_tonemap_tiles over device arrays on `stream` of the current device
+int enqueue_tonemap_tiles(const float* d_sum, uint32_t w, uint32_t h, const uint32_t* d_tile_samples, uint8_t* d_rgb8,
+                          hipStream_t stream);
 // enqueue one closest-hit query of n rays (rtw_ray[n] -> rtw_hit[n], device arrays) on `stream` of c.device, which
 // must be current; ev0 / ev1 (or NULL) are recorded around the kernel
 int enqueue_hit_rays(Scene& s, DeviceCopy& c, uint64_t n, const void* d_rays, void* d_hits, hipStream_t stream,
