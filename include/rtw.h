@@ -333,6 +333,47 @@ int rtw_render_adaptive(rtw_scene* s, const rtw_camera* cam, const float backgro
 int rtw_tonemap_tiles_device(int device, const float* d_rgb_sum, uint32_t w, uint32_t h,
                              const uint32_t* d_tile_samples, uint8_t* d_rgb8, void* stream);
 
+/* ---- feature buffers: what a denoiser behind a few-sample frame wants as guides -- first-hit albedo, normal and
+ *      depth per pixel, summed over the pixel's camera rays.  For pixel (j, i) and sample s the ray is rtw_camera_rays'
+ *      ray for (seed, j, i, s) (it does not depend on spp), its stream word the generator's state after the time draw,
+ *      and the record what rtw_hit_rays returns for that ray (same walk, same winner; the stream word keys a
+ *      ConstantMedium's free path).  The sample's features:
+ *        albedo (3 f32): a hit: what rtw_scatter_rays gives as the attenuation of a scattered ray or the emission of a
+ *                        light -- a Lambertian's / Isotropic's / DiffuseLight's texture value at (u, v, p), (1, 1, 1)
+ *                        for a Dielectric -- and for a Metal its albedo colour whether or not this ray would be
+ *                        absorbed (rtw_scatter_rays reports attenuation 0 there); a miss: `background`;
+ *        normal (3 f32): rtw_hit::normal as it stands (it faces the ray; not normalised where a triangle interpolates
+ *                        vertex normals); a miss: +0;
+ *        depth  (2 f32): (t, 1.0f); a miss: (+0, +0).  The second channel sums to the pixel's hit count, its coverage:
+ *                        divide by the samples for means, or by the count for the mean depth of what was hit.
+ *      No draw is made beyond the camera's.  Each buffer holds, per pixel and channel, x = x + f_s for s in sample order
+ *      (one f32 rounding per sample), added onto what it already holds: zeroed buffers give a fresh frame, and samples
+ *      [a, b) added onto the sums of [0, a) are the sums of [0, b) bit for bit, however the range is cut -- the property
+ *      rtw_render_samples_device's colour sums have, so both cut alike. */
+/* Samples [sample_first, sample_first + n_samples) of every pixel of the tile set, ADDED onto the DEVICE buffers: one
+ * fused kernel in place of rtw_camera_rays_device -> rtw_hit_rays_device -> rtw_scatter_rays_device and a per-pixel sum.
+ * Tile arguments, layouts, stream and RTW_FLAG_FULL_IMAGE as rtw_render_samples_device (tile ids must not repeat);
+ * d_albedo and d_normal have d_sum's layout (w*h*3, or packed [n_tiles][64][3]), d_depth two floats per pixel (w*h*2,
+ * or packed [n_tiles][64][2]).  Each of the three may be NULL, not all.  Pixels outside the image, tiles not named and
+ * ids beyond the last tile are left untouched.  Checks in rtw_render_samples_device's order and with its codes: a NULL
+ * argument (all three buffers NULL among them), then a flag other than RTW_FLAG_FULL_IMAGE (both RTW_EINVAL), an
+ * uncommitted scene (RTW_ESTATE), an image under 2x2, sample_first + n_samples > 2^31 (RTW_EINVAL), the device copy
+ * (RTW_ENODEV), then a pending traversal fault, an image side over 65536 and a camera shutter outside the committed
+ * motion range (RTW_EINVAL).  n_samples = 0 is RTW_OK and touches nothing.  The call only enqueues unless
+ * stats != NULL; stats: rays = paths = the samples traced, counted on the device, kernel_ms, total_ms.  The kernel is
+ * the scene's own variant beside its path kernel; it uses the (scene, device) pair's spill area and counter words, so
+ * the call must be serialised with the pair's renders and queries on one stream, as they are among themselves. */
+int rtw_render_features_device(rtw_scene* s, int device, const rtw_camera* cam, const float background[3],
+                               uint32_t w, uint32_t h, uint32_t sample_first, uint32_t n_samples, uint64_t seed,
+                               const uint32_t* d_tile_ids, uint32_t n_tiles, float* d_albedo, float* d_normal,
+                               float* d_depth, void* stream, uint32_t flags, rtw_stats* stats);
+/* The host form: blocking, on the first device copy; a fresh frame of spp samples (<= 2^31) over every tile into the
+ * host arrays albedo[w*h*3], normal[w*h*3], depth[w*h*2] in rtw_render's layout (row r <-> j = h-1-r), i.e.
+ * rtw_render_features_device of samples [0, spp) onto zeroed buffers.  Any of the three may be NULL, not all.  The
+ * device buffers belong to the device copy and are grown once.  spp = 0 gives zeros. */
+int rtw_render_features(rtw_scene* s, const rtw_camera* cam, const float background[3], uint32_t w, uint32_t h,
+                        uint32_t spp, uint64_t seed, float* albedo, float* normal, float* depth, rtw_stats* stats);
+
 /* ---- closest-hit ray queries: Hittable::hit(&ray, t_min, t_max) -> Option<HitRecord> on the world list
  *      (hittable/mod.rs:22-69) for rays the caller chooses.  A query is world.hit(ray, 0.001, +inf), the interval of
  *      lib.rs:102 and the only one the render's culling is proven for: t_min and t_max are not parameters.  The winner

@@ -179,6 +179,11 @@ _SIGS = {
                                       C.POINTER(rtw_stats)]),
     "rtw_tonemap_tiles_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                            C.c_void_p]),
+    "rtw_render_features_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(rtw_camera), _F, C.c_uint32, C.c_uint32,
+                                             C.c_uint32, C.c_uint32, C.c_uint64, _U32, C.c_uint32, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(rtw_stats)]),
+    "rtw_render_features": (C.c_int, [C.c_void_p, C.POINTER(rtw_camera), _F, C.c_uint32, C.c_uint32, C.c_uint32,
+                                      C.c_uint64, _F, _F, _F, C.POINTER(rtw_stats)]),
     "rtw_hit_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(rtw_ray), C.POINTER(rtw_hit),
                                C.POINTER(rtw_stats)]),
     "rtw_hit_rays_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -777,6 +782,38 @@ class Raytracer:
             self.scene._p, device, C.byref(self.cam.c), _fp(self.bg), self.w, self.h, min_spp, self.spp, self.max_depth,
             self.seed, threshold, C.c_void_p(d_sum_ptr), C.c_void_p(d_sq_ptr), C.c_void_p(d_tile_samples_ptr),
             C.c_void_p(d_tile_err_ptr) if d_tile_err_ptr else None, C.c_void_p(stream_ptr), flags,
+            C.byref(st) if want_stats else None))
+        return st.as_dict() if want_stats else None
+
+    def render_features(self, want=("albedo", "normal", "depth")):
+        """The denoiser's guides for this frame (rtw_render_features): per pixel the sums over its spp camera rays of the
+        first hit's albedo[h, w, 3], normal[h, w, 3] and depth[h, w, 2] = (t, 1) (the background, +0 and (0, 0) for a
+        miss; the second depth channel is the hit count), in render()'s row order.  Sample s is render()'s camera ray s.
+        -> ({name: array for the names in `want`}, stats)."""
+        names = ("albedo", "normal", "depth")
+        bad = [n for n in want if n not in names]
+        if bad:
+            raise ValueError(f"unknown feature buffers {bad}: {names}")
+        out = {n: np.empty((self.h, self.w, 2 if n == "depth" else 3), np.float32) for n in names if n in want}
+        st = rtw_stats()
+        _check(lib().rtw_render_features(self.scene._p, C.byref(self.cam.c), _fp(self.bg), self.w, self.h, self.spp,
+                                         self.seed, *[_fp(out[n]) if n in out else None for n in names], C.byref(st)))
+        return out, st.as_dict()
+
+    def render_features_device(self, d_albedo_ptr: int = 0, d_normal_ptr: int = 0, d_depth_ptr: int = 0,
+                               sample_first: int = 0, n_samples=None, device: int = 0, d_tiles_ptr: int = 0,
+                               n_tiles: int = 0, stream_ptr: int = 0, flags: int = 0, want_stats: bool = False):
+        """Enqueue the features of samples [sample_first, sample_first + n_samples) (n_samples = None: up to the frame's
+        spp), ADDED in sample order onto the device sums (3, 3 and 2 floats per pixel; 0 = not wanted, not all three);
+        tiles, layouts and flags as render_samples_device.  Chunks that cover [0, spp) give render_features()' buffers
+        bit for bit."""
+        n = max(self.spp - sample_first, 0) if n_samples is None else n_samples
+        st = rtw_stats()
+        _check(lib().rtw_render_features_device(
+            self.scene._p, device, C.byref(self.cam.c), _fp(self.bg), self.w, self.h, sample_first, n, self.seed,
+            C.cast(C.c_void_p(d_tiles_ptr), _U32) if d_tiles_ptr else None, n_tiles,
+            C.c_void_p(d_albedo_ptr) if d_albedo_ptr else None, C.c_void_p(d_normal_ptr) if d_normal_ptr else None,
+            C.c_void_p(d_depth_ptr) if d_depth_ptr else None, C.c_void_p(stream_ptr), flags,
             C.byref(st) if want_stats else None))
         return st.as_dict() if want_stats else None
 

@@ -18,6 +18,7 @@
 //   raytracer.sample_ray(&ray, rng, depth) -> Color      world.sample_rays(rays, background, max_depth) -> std::vector<Sample>  lib.rs:97-117
 //   (no counterpart: the frame in growing steps)        Raytracer(..).render_progressive(on_frame, step); sample_blocks; tonemap_device
 //   (no counterpart: a sample count per 8x8 tile)       Raytracer(..).render_adaptive(threshold, min_spp) -> AdaptiveFrame; tile_noise_device; tonemap_tiles
+//   (no counterpart: a denoiser's guides)               Raytracer(..).render_features() -> FeatureFrame; render_features_device
 // Errors (the reference panics) throw rtw::Error with rtw_last_error()'s message.
 #pragma once
 #include <stdexcept>
@@ -240,6 +241,12 @@ struct AdaptiveFrame {
   std::vector<float> tile_err;
 };
 
+// Raytracer::render_features' frame: per pixel, in render_sums' order, the sums over its camera rays of the first hit's
+// albedo (3 floats), normal (3) and depth (2: t and the hit count)
+struct FeatureFrame {
+  std::vector<float> albedo, normal, depth;
+};
+
 // lib.rs:40-95
 class Raytracer {
  public:
@@ -308,6 +315,26 @@ class Raytracer {
     const float bg[3] = {bg_.x, bg_.y, bg_.z};
     check(rtw_render_adaptive_device(world_.raw(), device, &cam_.c, bg, w_, h_, min_spp, spp_, depth_, seed_, threshold,
                                      d_sum, d_sq, d_tile_samples, d_tile_err, stream, flags, st));
+  }
+  // The denoiser's guides for this frame (rtw_render_features): first-hit albedo, normal and depth summed over each
+  // pixel's spp camera rays (the background, +0 and (0, 0) for a miss); sample s is render_sums' camera ray s
+  FeatureFrame render_features(rtw_stats* st = nullptr) const {
+    const size_t px = (size_t)w_ * h_;
+    FeatureFrame f{std::vector<float>(px * 3), std::vector<float>(px * 3), std::vector<float>(px * 2)};
+    const float bg[3] = {bg_.x, bg_.y, bg_.z};
+    check(rtw_render_features(world_.raw(), &cam_.c, bg, w_, h_, spp_, seed_, f.albedo.data(), f.normal.data(),
+                              f.depth.data(), st));
+    return f;
+  }
+  // Samples [first, first + n) of the tile set as features added onto the device sums d_albedo, d_normal (3 floats per
+  // pixel) and d_depth (2), each or nullptr, not all (rtw_render_features_device; the constructor's spp is not used);
+  // tiles, layouts and flags as render_samples_device
+  void render_features_device(int device, uint32_t first, uint32_t n, float* d_albedo, float* d_normal, float* d_depth,
+                              const uint32_t* d_tile_ids = nullptr, uint32_t n_tiles = 0, void* stream = nullptr,
+                              uint32_t flags = 0, rtw_stats* st = nullptr) const {
+    const float bg[3] = {bg_.x, bg_.y, bg_.z};
+    check(rtw_render_features_device(world_.raw(), device, &cam_.c, bg, w_, h_, first, n, seed_, d_tile_ids, n_tiles,
+                                     d_albedo, d_normal, d_depth, stream, flags, st));
   }
 
  private:

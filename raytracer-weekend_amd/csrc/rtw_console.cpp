@@ -2,12 +2,15 @@
 //
 //   rtw_console <scene> [-w|--width 400] [-a|--aspect-ratio 1.7777778] [-s|--samples-per-pixel 100]
 //               [--seed 0] [--models models] [--out render] [--progressive STEP] [--adaptive THRESHOLD [--min-spp 16]]
+//               [--features]
 // Same Opts and defaults (main.rs:15-26), height = round(width / aspect) (:33), camera
 // aspect = width / height as f32 (:38-41), tonemap (:68-90), PNG to render/image_0000.png (:92-94).
 // --progressive (no counterpart in console_app) renders each frame through rtw_render_progressive: the PNG is rewritten
 // after every step, and its last version is the one-shot frame's file byte for byte.
 // --adaptive renders each frame through rtw_render_adaptive with -s as the most samples a tile gets, and writes the PNG
 // through rtw_tonemap_tiles: every 8x8 tile is the one-shot frame's at the sample count it stopped at.
+// --features writes, beside each frame's PNG, the denoiser's guides from rtw_render_features at the frame's spp:
+// albedo_NNNN.png (rtw_tonemap of the albedo sums) and normal_NNNN.png (the summed normal's direction, 0.5 + 0.5 n).
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -80,10 +83,24 @@ static double mean_rel_stderr(const float* sum, const float* sq, size_t n_pixels
   return lit ? tot / (double)lit : 0.0;
 }
 
+// --features' normal image: per channel u8(255.999 * clamp(0.5 + 0.5 * N_c / |N|, 0, 0.999)) of the pixel's summed
+// normal N; a zero N gives 0.5
+static void normal_rgb8(const float* n, size_t n_pixels, uint8_t* rgb) {
+  for (size_t p = 0; p < n_pixels; ++p) {
+    const float x = n[p * 3], y = n[p * 3 + 1], z = n[p * 3 + 2];
+    const float len = sqrtf(x * x + y * y + z * z);
+    for (int c = 0; c < 3; ++c) {
+      float v = len > 0.0f ? 0.5f + 0.5f * (n[p * 3 + c] / len) : 0.5f;
+      v = v < 0.0f ? 0.0f : (v > 0.999f ? 0.999f : v);
+      rgb[p * 3 + c] = v == v ? (uint8_t)(255.999f * v) : (uint8_t)0;
+    }
+  }
+}
+
 int main(int argc, char** argv) {
   std::string scene, models = "models", out_dir = "render";
   uint32_t width = 400, spp = 100, step = 0, min_spp = 16;
-  bool progressive = false, adaptive = false;
+  bool progressive = false, adaptive = false, features = false;
   float threshold = 0.0f;
   double aspect = 1.7777778;
   uint64_t seed = 0;
@@ -101,12 +118,13 @@ int main(int argc, char** argv) {
     else if (a == "--out") out_dir = next("--out");
     else if (a == "--progressive") { progressive = true; step = (uint32_t)atoi(next("--progressive")); }
     else if (a == "--adaptive") { adaptive = true; threshold = (float)atof(next("--adaptive")); }
+    else if (a == "--features") features = true;
     else if (a == "--min-spp") min_spp = (uint32_t)atoi(next("--min-spp"));
     else if (a == "-h" || a == "--help") {
       printf("usage: rtw_console <jumpy-balls|two-spheres|two-perlin-spheres|earth|simple-light|cornell-box|"
              "smokey-cornell-box|book2-final-scene|animated-book2-final-scene|simple-triangle|wavefront-cow-obj|"
              "wavefront-suspension-obj|textured-monument> [-w W] [-a ASPECT] [-s SPP] [--seed N] [--models DIR] "
-             "[--out DIR] [--progressive STEP] [--adaptive THRESHOLD [--min-spp N]]\n"
+             "[--out DIR] [--progressive STEP] [--adaptive THRESHOLD [--min-spp N]] [--features]\n"
              "  --progressive STEP  render each frame in growing steps (1, 2, 4, ... samples while the doubled count is\n"
              "      within STEP, then STEP at a time; 0 = doubling to the end); after every step the frame's PNG is\n"
              "      rewritten and the samples done and the mean relative standard error are printed.  That error, from\n"
@@ -118,7 +136,10 @@ int main(int argc, char** argv) {
              "  --adaptive THRESHOLD [--min-spp N]  a sample count per 8x8 tile: every tile gets N (default 16) samples,\n"
              "      then 2 N, 4 N, ... up to SPP, and stops at the first count at which its noise estimate (rtw.h: the\n"
              "      tile's root mean variance of the mean over its mean brightness + 0.03) is <= THRESHOLD.  Prints the\n"
-             "      number of tiles per sample count.\n");
+             "      number of tiles per sample count.\n"
+             "  --features  also write the denoiser's guides of each frame, first-hit features summed over the pixel's\n"
+             "      SPP camera rays: albedo_NNNN.png (the albedo sums through the image's tonemap) and normal_NNNN.png\n"
+             "      (per channel 255.999 clamp(0.5 + 0.5 N_c / |N|, 0, 0.999) of the summed normal N; 0.5 where N = 0).\n");
       return 0;
     } else if (scene.empty()) scene = a;
     else { fprintf(stderr, "unexpected argument '%s'\n", a.c_str()); return 2; }
@@ -163,6 +184,17 @@ int main(int argc, char** argv) {
         std::vector<float> sums = rt.render_sums(&st);
         rtw::check(rtw_tonemap(sums.data(), width * height, spp, img.data()));
         if (!write_png(path.c_str(), img.data(), width, height)) { fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
+      }
+      if (features) {
+        const rtw::FeatureFrame ff = rt.render_features();
+        snprintf(name, sizeof name, "/albedo_%04zu.png", frame);
+        const std::string apath = out_dir + name;
+        rtw::check(rtw_tonemap(ff.albedo.data(), width * height, spp, img.data()));
+        if (!write_png(apath.c_str(), img.data(), width, height)) { fprintf(stderr, "cannot write %s\n", apath.c_str()); return 1; }
+        snprintf(name, sizeof name, "/normal_%04zu.png", frame);
+        const std::string npath = out_dir + name;
+        normal_rgb8(ff.normal.data(), (size_t)width * height, img.data());
+        if (!write_png(npath.c_str(), img.data(), width, height)) { fprintf(stderr, "cannot write %s\n", npath.c_str()); return 1; }
       }
       printf("%s %ux%u %u spp: %.1f ms kernel, %llu rays, %.1f Mrays/s -> %s\n", scene.c_str(), width, height, spp,
              st.kernel_ms, (unsigned long long)st.rays, st.rays / (st.kernel_ms * 1e3), path.c_str());

@@ -2,7 +2,7 @@
 // that are no templates (reduce_kernel, unpack_tiles_kernel, tile_list_kernel with its diagnostic calls, the libm and
 // reciprocal diagnostics, with the two calls that launch the latter), the tuning knobs, pick_kernel (which path-kernel variant a scene runs) and the launches
 // (enqueue_render, enqueue_render_samples, enqueue_tonemap, enqueue_tile_noise, enqueue_tonemap_tiles, enqueue_hit_rays,
-// enqueue_sample_rays, enqueue_scatter_rays, enqueue_camera_rays, enqueue_unpack),
+// enqueue_sample_rays, enqueue_scatter_rays, enqueue_camera_rays, enqueue_features, enqueue_unpack),
 // which share one cache of resident grids (resident_blocks), the walk's tuning (tune_walk) and the one-record-per-lane
 // queries' launch (launch_query).  The
 // scene's device copies, statistics and the render entry points are plain HIP runtime code in rtw_render.cpp, the
@@ -886,6 +886,52 @@ int enqueue_camera_rays(DeviceCopy& c, const Frame& f, uint64_t first, uint64_t 
                                        "camera_rays_kernel", kn.verbose);
   return launch_query(dev::camera_rays_kernel, "camera_rays_kernel launch", resident, dev::SHADE_BLOCK, n, a, stream,
                       ev0, ev1);
+}
+
+// Feature buffers (rtw_render_features*): the scene's variant as its renders pick it, the feature kernel's own resident
+// capacity as the largest grid (one wave per tile slot), the walk's launch tuning as a render's, frame_args' camera
+// operands.  The counters are zeroed on the stream first: the kernel adds the samples it traced to the first word.
+int enqueue_features(Scene& sc, DeviceCopy& c, const Frame& f, uint32_t sample_first, const TileSet& ts,
+                     float* d_albedo, float* d_normal, float* d_depth, hipStream_t stream, hipEvent_t ev0,
+                     hipEvent_t ev1) {
+  if (int e = check_guard(c)) return e;
+  if (int e = check_image_max(f.w, f.h)) return e;
+  if (int e = check_shutter(*f.cam, sc.flat)) return e;
+  const Knobs kn = read_knobs();
+  const Variant var = path_kernel_variant(sc.flat, kn);
+  const KernelCfg& k = var.cfg;
+  const int resident = resident_blocks(c, GRID_FEATURE, (const void*)var.feature, k.blk, "feature kernel", kn.verbose);
+  const WalkTuning t = tune_walk(kn, sc.flat, k, resident);
+  if (int e = grow(c.spill, (size_t)t.spill_depth * t.spill_lanes * sizeof(int32_t))) return e;
+  Frame f0 = f;
+  f0.sample_base = 0;  // the key's sample word is the kernel's own s
+  const RenderArgs r = frame_args(c, f0, ts, nullptr);
+  FeatureArgs a;
+  memset(&a, 0, sizeof a);
+  a.scene = c.scene;
+  a.mshade = static_cast<const DevShade*>(c.mshade.p);
+  a.cam = r.cam;
+  memcpy(a.bg, f.bg, sizeof a.bg);
+  a.fw1 = r.fw1; a.fh1 = r.fh1; a.rw1 = r.rw1; a.rh1 = r.rh1; a.time_span = r.time_span;
+  a.w = f.w; a.h = f.h; a.tiles_x = r.tiles_x;
+  a.n_tiles = (uint32_t)f.tiles();
+  a.seed_hash = r.seed_hash;
+  a.sample_first = sample_first;
+  a.n_samples = f.spp;
+  a.tile_ids = ts.ids;
+  a.n_slots = ts.n;
+  a.packed = r.packed_out;
+  a.albedo = d_albedo;
+  a.normal = d_normal;
+  a.depth = d_depth;
+  a.leaf16 = t.leaf16;
+  a.spill_lanes = t.spill_lanes;
+  a.spill = static_cast<int32_t*>(c.spill.p);
+  a.err = c.err_host;
+  a.counters = c.counters;
+  HIPCHK(hipMemsetAsync(c.counters, 0, COUNTER_WORDS * sizeof(unsigned long long), stream), "hipMemsetAsync");
+  // one wave per tile slot
+  return launch_query(var.feature, "feature_kernel launch", resident, k.blk, (uint64_t)ts.n * 64u, a, stream, ev0, ev1);
 }
 
 int enqueue_unpack(uint32_t w, uint32_t h, const uint32_t* d_tiles, uint32_t n_tiles, const float* d_packed,

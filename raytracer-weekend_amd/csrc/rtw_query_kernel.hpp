@@ -65,6 +65,24 @@ __device__ __forceinline__ uint64_t load_ray(const void* rays, uint64_t i, Ray& 
   return ray_of(load_ray(rays, i), ray);
 }
 
+// start_path's ray (rtw_path_kernel.hpp, AB = false; lib.rs:84-86 + camera.rs:66-74) for pixel (j, i), sample s: the
+// generator keyed by (seed_hash, j, i, s), its draws in start_path's order (u, v, the lens disk, the time) and the same
+// f32 operations; fw1 .. time_span are RenderArgs'.  -> the generator's state after the time draw (the stream word).
+// The one body camera_rays_kernel (rtw_shade_kernel.hpp) and feature_kernel (rtw_feature_kernel.hpp) both call.
+__device__ __forceinline__ uint64_t camera_ray(const DevCamera& C, float fw1, float fh1, float rw1, float rh1,
+                                               float time_span, uint64_t seed_hash, uint32_t j, uint32_t i, uint32_t s,
+                                               Ray& ray) {
+  uint64_t rng = xoro_seed(splitmix64(seed_hash ^ (((uint64_t)j << 48) | ((uint64_t)i << 32) | s)));
+  const float u = div_by_recip((float)i + gen_f32(rng), fw1, rw1);
+  const float v = div_by_recip((float)j + gen_f32(rng), fh1, rh1);
+  const V3 rd = scale(rand_in_unit_disk<false>(rng), C.lens_radius);
+  const V3 off = add(scale(ld3(C.u), rd.x), scale(ld3(C.v), rd.y));
+  ray.o = add(ld3(C.origin), off);
+  ray.d = sub(sub(add(add(ld3(C.llc), scale(ld3(C.horizontal), u)), scale(ld3(C.vertical), v)), ld3(C.origin)), off);
+  ray.time = gen_range<false>(rng, C.time0, C.time1, time_span);
+  return rng;
+}
+
 // Each lane owns one ray and a wave takes 64 consecutive ones (the caller's order decides coherence); grid-stride
 // over n, the grid at most the resident capacity, so an LDS-node workgroup copies its node table once.  The last
 // wave runs partial under its exec mask.

@@ -123,7 +123,7 @@ void release(Scene& s) {
     if (c.err_host) hipHostFree(c.err_host);
     if (c.lists_count) hipFree(c.lists_count);
     for (DevBuf* b : {&c.sbuf, &c.spill, &c.image, &c.tiles, &c.packed, &c.gathered, &c.gather_ids, &c.qrays, &c.qhits,
-                       &c.mshade, &c.qscatter, &c.qsamples, &c.pboxes, &c.tile_lists, &c.film_sum, &c.film_sq,
+                       &c.mshade, &c.qscatter, &c.qsamples, &c.pboxes, &c.tile_lists, &c.film_sum, &c.film_sq, &c.feat_albedo, &c.feat_normal, &c.feat_depth,
                        &c.adapt_ids, &c.adapt_tiles})
       free_buf(*b);
     if (c.adapt_host) hipHostFree(c.adapt_host);
@@ -180,6 +180,14 @@ static int check_sample_range(uint32_t first, uint32_t n) {
   if ((uint64_t)first + n > (1ull << 31))
     return fail(RTW_EINVAL, "samples [%u, %u + %u) go beyond 2^31", first, first, n);
   return RTW_OK;
+}
+
+// the feature calls' checks before the sample range: check_frame's (`out`: one of the three buffers is there), with
+// the flags between its NULL test and the scene's state
+static int check_features(const rtw_scene* s, const Frame& f, bool out, uint32_t flags) {
+  if (!s || !f.cam || !f.bg || !out) return fail(RTW_EINVAL, "NULL argument");
+  if (flags & ~(uint32_t)RTW_FLAG_FULL_IMAGE) return fail(RTW_EINVAL, "flags %#x: RTW_FLAG_FULL_IMAGE only", flags);
+  return check_frame(s, f, out, true);
 }
 
 // the adaptive calls' threshold: err <= threshold must be able to hold and to fail
@@ -412,6 +420,82 @@ int rtw_render_samples_device(rtw_scene* s, int device, const rtw_camera* cam, c
     out.total_ms = ms_since(t0);
     *stats = out;
   }
+  return rc;
+}
+
+int rtw_render_features_device(rtw_scene* s, int device, const rtw_camera* cam, const float bg[3], uint32_t w,
+                               uint32_t h, uint32_t sample_first, uint32_t n_samples, uint64_t seed,
+                               const uint32_t* d_tiles, uint32_t n_tiles, float* d_albedo, float* d_normal,
+                               float* d_depth, void* stream, uint32_t flags, rtw_stats* stats) {
+  auto t0 = std::chrono::steady_clock::now();
+  const Frame f{cam, bg, w, h, n_samples, 1, seed};
+  if (int e = check_features(s, f, d_albedo || d_normal || d_depth, flags)) return e;
+  if (int e = check_sample_range(sample_first, n_samples)) return e;
+  DeviceCopy* c = need_copy(s->s, device);
+  if (!c) return RTW_ENODEV;
+  TileSet ts{d_tiles, 0, 1, d_tiles ? n_tiles : (uint32_t)f.tiles()};
+  ts.full = (flags & RTW_FLAG_FULL_IMAGE) != 0;
+  if (n_samples == 0) {  // nothing to add: nothing enqueued
+    if (stats) *stats = rtw_stats{};
+    return RTW_OK;
+  }
+  DeviceGuard g;
+  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
+  if (stats)
+    if (int e = copy_events(*c)) return e;
+  const hipEvent_t e0 = stats ? c->ev[0] : nullptr, e1 = stats ? c->ev[1] : nullptr;
+  const hipStream_t st = abi_stream(stream);
+  int rc = enqueue_features(s->s, *c, f, sample_first, ts, d_albedo, d_normal, d_depth, st, e0, e1);
+  if (rc == RTW_OK && stats) {
+    rtw_stats out{};
+    rc = collect_stats(*c, st, e0, e1, 0, &out);
+    out.paths = out.rays;  // the samples the kernel traced, counted on the device
+    out.total_ms = ms_since(t0);
+    *stats = out;
+  }
+  return rc;
+}
+
+int rtw_render_features(rtw_scene* s, const rtw_camera* cam, const float bg[3], uint32_t w, uint32_t h, uint32_t spp,
+                        uint64_t seed, float* albedo, float* normal, float* depth, rtw_stats* stats) {
+  auto t0 = std::chrono::steady_clock::now();
+  const Frame f{cam, bg, w, h, spp, 1, seed};
+  if (int e = check_features(s, f, albedo || normal || depth, 0)) return e;
+  if (int e = check_sample_range(0, spp)) return e;
+  DeviceCopy* c = need_copy(s->s, -1, nullptr);
+  if (!c) return RTW_ENODEV;
+  if (int e = check_image_max(w, h)) return e;
+  DeviceGuard g;
+  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
+  if (int e = copy_events(*c)) return e;
+  const size_t px = (size_t)w * h;
+  struct Buf {
+    DevBuf& buf;
+    float* host;
+    size_t bytes;
+  } bufs[3] = {{c->feat_albedo, albedo, px * 3 * sizeof(float)},
+               {c->feat_normal, normal, px * 3 * sizeof(float)},
+               {c->feat_depth, depth, px * 2 * sizeof(float)}};
+  float* d[3] = {nullptr, nullptr, nullptr};
+  for (int k = 0; k < 3; ++k) {
+    if (!bufs[k].host) continue;
+    if (int e = grow(bufs[k].buf, bufs[k].bytes)) return e;  // kept for the next frame, as rtw_render's image
+    d[k] = static_cast<float*>(bufs[k].buf.p);
+    HIPCHK(hipMemsetAsync(d[k], 0, bufs[k].bytes, nullptr), "hipMemsetAsync(features)");
+  }
+  const TileSet all{nullptr, 0, 1, (uint32_t)f.tiles()};
+  rtw_stats st{};
+  int rc = RTW_OK;
+  if (spp) {
+    rc = enqueue_features(s->s, *c, f, 0, all, d[0], d[1], d[2], nullptr, c->ev[0], c->ev[1]);
+    if (rc == RTW_OK) rc = collect_stats(*c, nullptr, c->ev[0], c->ev[1], 0, &st);
+    st.paths = st.rays;
+  }
+  for (int k = 0; k < 3 && rc == RTW_OK; ++k)
+    if (d[k] && hipMemcpy(bufs[k].host, d[k], bufs[k].bytes, hipMemcpyDeviceToHost) != hipSuccess)
+      rc = fail(RTW_ENODEV, "hipMemcpy(features)");
+  st.total_ms = ms_since(t0);
+  if (stats) *stats = st;
   return rc;
 }
 

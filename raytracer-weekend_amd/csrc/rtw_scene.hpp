@@ -103,7 +103,7 @@ struct ResidentGrid {
   const void* fn = nullptr;
   int blocks = 0;
 };
-enum GridSlot { GRID_PATH, GRID_PATH_COUNT, GRID_HIT, GRID_SCATTER, GRID_CAMERA, GRID_SAMPLE, GRID_SLOTS };
+enum GridSlot { GRID_PATH, GRID_PATH_COUNT, GRID_HIT, GRID_SCATTER, GRID_CAMERA, GRID_SAMPLE, GRID_FEATURE, GRID_SLOTS };
 
 struct DeviceCopy {
   int device = -1;  // the logical device the caller names (rtw_render_device, rtw_render_multi's device d)
@@ -119,10 +119,11 @@ struct DeviceCopy {
   DevBuf spill;                            // traversal-stack overflow (trees deeper than the LDS stack)
   hipEvent_t kev[64][2] = {};              // pairs around path-kernel launches (ring, rtw_path_kernel_times)
   uint32_t kev_head = 0, kev_count = 0;
-  ResidentGrid grids[GRID_SLOTS];          // the path kernel (plain, counting) and the four query kernels
+  ResidentGrid grids[GRID_SLOTS];          // the path kernel (plain, counting), the four query kernels and the feature kernel
   // device buffers kept across render calls (grown, never shrunk; freed by release()): a
   // 30-camera animation through rtw_render does no hipMalloc after the first frame
   DevBuf image, tiles, packed, gathered, gather_ids;
+  DevBuf feat_albedo, feat_normal, feat_depth;  // rtw_render_features' device sums (grown once)
   DevBuf film_sum, film_sq;                // rtw_render_progressive's device sums: the frame's Σ x and Σ x^2
   // rtw_render_adaptive*: two tile-id lists of the frame's tile count and the count word behind them (grown once),
   // the pinned host word the count is read back into, and the host form's per-tile counts and errors
@@ -304,6 +305,13 @@ int enqueue_camera_rays(DeviceCopy& c, const Frame& f, uint64_t first, uint64_t 
 // recorded around them.  Afterwards c.counters[0] holds the segments traced.
 int enqueue_sample_rays(Scene& s, DeviceCopy& c, uint64_t n, const void* d_rays, const float* bg, uint32_t max_depth,
                         void* d_samples, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1);
+// enqueue samples [sample_first, sample_first + n_samples) of the tiles' pixels as first-hit features, ADDED in sample
+// order onto what d_albedo, d_normal (3 floats per pixel) and d_depth (2 per pixel) hold (each may be NULL), on `stream`
+// of c.device, which must be current: enqueue_render_samples' checks and counters' reset, then one launch of the
+// scene's feature kernel.  Afterwards c.counters[0] holds the samples traced.  The caller has checked the range.
+int enqueue_features(Scene& s, DeviceCopy& c, const Frame& f, uint32_t sample_first, const TileSet& tiles,
+                     float* d_albedo, float* d_normal, float* d_depth, hipStream_t stream, hipEvent_t ev0,
+                     hipEvent_t ev1);
 int enqueue_unpack(uint32_t w, uint32_t h, const uint32_t* d_tiles, uint32_t n_tiles, const float* d_packed,
                    float* d_image, hipStream_t stream);
 

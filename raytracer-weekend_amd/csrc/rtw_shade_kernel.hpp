@@ -53,16 +53,10 @@ __global__ __launch_bounds__(SHADE_BLOCK) void camera_rays_kernel(CameraRaysArgs
     const uint64_t row = p / a.row_paths, in_row = p - row * a.row_paths;
     const uint32_t i = (uint32_t)(in_row / a.spp), s = (uint32_t)(in_row - (uint64_t)i * a.spp);
     const uint32_t j = a.h1 - (uint32_t)row;
-    uint64_t rng = xoro_seed(splitmix64(a.seed_hash ^ (((uint64_t)j << 48) | ((uint64_t)i << 32) | s)));
-    // lib.rs:84-86 + camera.rs:66-74
-    const float u = div_by_recip((float)i + gen_f32(rng), a.fw1, a.rw1);
-    const float v = div_by_recip((float)j + gen_f32(rng), a.fh1, a.rh1);
-    const V3 rd = scale(rand_in_unit_disk<false>(rng), C.lens_radius);
-    const V3 off = add(scale(ld3(C.u), rd.x), scale(ld3(C.v), rd.y));
-    const V3 o = add(ld3(C.origin), off);
-    const V3 d = sub(sub(add(add(ld3(C.llc), scale(ld3(C.horizontal), u)), scale(ld3(C.vertical), v)), ld3(C.origin)),
-                     off);
-    const float time = gen_range<false>(rng, C.time0, C.time1, a.time_span);
+    Ray r;
+    const uint64_t rng = camera_ray(C, a.fw1, a.fh1, a.rw1, a.rh1, a.time_span, a.seed_hash, j, i, s, r);
+    const V3 o = r.o, d = r.d;
+    const float time = r.time;
     RayRec q;
     q.q0.x = o.x; q.q0.y = o.y; q.q0.z = o.z; q.q0.w = d.x;
     q.q1.x = d.y; q.q1.y = d.z; q.q1.z = time; q.q1.w = 0.0f;
