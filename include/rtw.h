@@ -374,6 +374,62 @@ int rtw_render_features_device(rtw_scene* s, int device, const rtw_camera* cam, 
 int rtw_render_features(rtw_scene* s, const rtw_camera* cam, const float background[3], uint32_t w, uint32_t h,
                         uint32_t spp, uint64_t seed, float* albedo, float* normal, float* depth, rtw_stats* stats);
 
+/* ---- the denoiser: an edge-avoiding a-trous wavelet filter (a dilated 5x5 B3 spline per iteration) for few-sample
+ *      frames, over what the calls above leave on the device: the colour sums and sums of squares of
+ *      rtw_render_samples_device / rtw_render_adaptive_device and the guides of rtw_render_features_device.  It
+ *      filters the albedo-demodulated mean radiance; its edge stops come from normal, depth and luminance, the last
+ *      scaled by the per-pixel variance of the mean, which is carried through the iterations.  No counterpart in the
+ *      reference, so
+ *      the filter is DEFINED here, operation by operation: all arithmetic f32 with one rounding per operation (no fused
+ *      multiply-add), IEEE division and sqrt, no transcendentals; max0(v) is v > 0 ? v : 0 (a NaN gives 0).  The device
+ *      kernels, rtw_denoise's host loops and the tests' numpy restatement agree bit for bit.
+ *      Inputs, full w x h layout, rows as rtw_render: sum (3 floats per pixel), sq (3, may be NULL), albedo (3, may be
+ *      NULL), normal (3, may be NULL), depth (2, may be NULL).  A pixel's sample count n is `samples`, or with a table
+ *      tile_samples[t] of the pixel's 8x8 tile, t as rtw_tonemap_tiles finds it; the same n holds for all five buffers
+ *      (a progressive or adaptive loop hands both render calls the same ranges).
+ *      Prepare, per pixel, inv = 1.0f / (float)n, per channel c:
+ *        m_c = s_c * inv;  a_c = A_c * inv;  d_c = a_c > 0.001f ? a_c : 0.001f (1.0f without albedo);  x_c = m_c / d_c;
+ *        v_c = q_c * inv - m_c * m_c, v_c < 0 ? 0 : v_c (rtw_tile_noise_device's clamp: a NaN stays);
+ *        u_c = (v_c * inv) / (d_c * d_c);  var = (u_0 + u_1) + u_2  (+0 without sq);
+ *        nn = (N_0 N_0 + N_1 N_1) + N_2 N_2;  g_c = nn > 0 ? N_c / sqrt(nn) : +0  (+0 without normal);
+ *        z = T * inv with T the first depth channel (+0 without depth).
+ *      A pixel with n = 0 is empty: x_c a quiet NaN, var, g_c, z = +0, its output +0.
+ *      Iteration k = 0 .. iterations - 1, step = 1 << k, for pixel p, with the luminance
+ *        l(x) = (0.2126f x_0 + 0.7152f x_1) + 0.0722f x_2:
+ *        rz = 1.0f / ((sigma_z * (float)step) * fabsf(z_p) + 1e-6f);  rl = 1.0f / (sigma_l * sqrtf(var_p) + 1e-4f);
+ *        k_n = 1.0f / (sigma_n * sigma_n), computed once on the host.
+ *      Taps q = p + step * (dx, dy), dy = -2..2 outer, dx = -2..2 inner, those off the image skipped; H = {0.375, 0.25,
+ *      0.0625}; the tap's weight, built in this order:
+ *        w = H[|dx|] * H[|dy|];
+ *        w = w * max0(1 - dn2 * k_n), dn2 = (e_0 e_0 + e_1 e_1) + e_2 e_2, e = g_p - g_q   (dropped for sigma_n = 0);
+ *        w = w * max0(1 - fabsf(z_p - z_q) * rz)                                          (dropped for sigma_z = 0);
+ *        w = w * max0(1 - fabsf(l(x_p) - l(x_q)) * rl)                     (dropped for sigma_l = 0 or without sq).
+ *      A tap counts only if w > 0 and l(x_q) == l(x_q); then sw = sw + w, sx_c = sx_c + w * x_q,c and
+ *      sv = sv + (w * w) * var_q, in tap order: the order is the contract.  If sw > 0: x'_c = sx_c / sw and
+ *      var' = sv / (sw * sw); otherwise the pixel keeps x and var.  The guides do not change between iterations.
+ *      Finish: out_c = x_c * d_c, the mean radiance (rtw_tonemap* with spp = 1 makes the preview); +0 for an empty
+ *      pixel.
+ *      Both calls answer RTW_EINVAL for, in this order: a NULL sum, out or (device call) scratch; an image under 2x2
+ *      or over 65536 a side; samples = 0 without a tile table; iterations > 10; a sigma that is NaN, negative or
+ *      infinite (sigma_l, sigma_n, sigma_z in turn).  iterations = 0 is valid: prepare, then finish. */
+/* The bytes of device scratch rtw_denoise_device needs for a w x h image (host only; the only place that knows the
+ * size: the ping-pong images and the prepared guides).  RTW_EINVAL: bytes NULL, then an image under 2x2 or over 65536
+ * a side. */
+int rtw_denoise_scratch_bytes(uint32_t w, uint32_t h, uint64_t* bytes);
+/* The filter over DEVICE arrays, enqueued on `stream` (no scene: what rtw_tonemap_device is to rtw_tonemap).
+ * device < 0 means the current device.  d_out (w*h*3 floats) may not alias an input.  d_scratch: at least
+ * rtw_denoise_scratch_bytes(w, h) bytes, 16-byte aligned (RTW_EINVAL after the checks above if not); its contents on
+ * entry do not matter, and nothing is written beyond that size or beyond d_out's w*h*3 floats. */
+int rtw_denoise_device(int device, const float* d_sum, const float* d_sq, const float* d_albedo, const float* d_normal,
+                       const float* d_depth, uint32_t w, uint32_t h, uint32_t samples, const uint32_t* d_tile_samples,
+                       uint32_t iterations, float sigma_l, float sigma_n, float sigma_z, float* d_out, void* d_scratch,
+                       void* stream);
+/* The same arithmetic as plain loops over HOST arrays, no GPU (rtw_tonemap's role beside rtw_tonemap_device);
+ * RTW_ENOMEM if its work arrays cannot be had. */
+int rtw_denoise(const float* rgb_sum, const float* rgb_sq_sum, const float* albedo, const float* normal,
+                const float* depth, uint32_t w, uint32_t h, uint32_t samples, const uint32_t* tile_samples,
+                uint32_t iterations, float sigma_l, float sigma_n, float sigma_z, float* out);
+
 /* ---- closest-hit ray queries: Hittable::hit(&ray, t_min, t_max) -> Option<HitRecord> on the world list
  *      (hittable/mod.rs:22-69) for rays the caller chooses.  A query is world.hit(ray, 0.001, +inf), the interval of
  *      lib.rs:102 and the only one the render's culling is proven for: t_min and t_max are not parameters.  The winner

@@ -184,6 +184,12 @@ _SIGS = {
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(rtw_stats)]),
     "rtw_render_features": (C.c_int, [C.c_void_p, C.POINTER(rtw_camera), _F, C.c_uint32, C.c_uint32, C.c_uint32,
                                       C.c_uint64, _F, _F, _F, C.POINTER(rtw_stats)]),
+    "rtw_denoise_scratch_bytes": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "rtw_denoise_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                     C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_float,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtw_denoise": (C.c_int, [_F, _F, _F, _F, _F, C.c_uint32, C.c_uint32, C.c_uint32, _U32, C.c_uint32, C.c_float,
+                              C.c_float, C.c_float, _F]),
     "rtw_hit_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(rtw_ray), C.POINTER(rtw_hit),
                                C.POINTER(rtw_stats)]),
     "rtw_hit_rays_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -240,6 +246,9 @@ _lib = None
 
 
 ABI_VERSION = 7  # include/rtw.h RTW_ABI_VERSION
+# the denoiser's starting point (denoise, denoise_device, Raytracer.render_denoised; rtw.hpp and rtw_console use the
+# same): DESIGN.md "Denoiser" has the error ratios they give
+DENOISE_ITERATIONS, DENOISE_SIGMA_L, DENOISE_SIGMA_N, DENOISE_SIGMA_Z = 5, 4.0, 0.5, 0.1
 
 
 def lib_sha() -> str:
@@ -816,6 +825,78 @@ class Raytracer:
             C.c_void_p(d_depth_ptr) if d_depth_ptr else None, C.c_void_p(stream_ptr), flags,
             C.byref(st) if want_stats else None))
         return st.as_dict() if want_stats else None
+
+    def render_denoised(self, iterations: int = DENOISE_ITERATIONS, sigma_l: float = DENOISE_SIGMA_L,
+                        sigma_n: float = DENOISE_SIGMA_N, sigma_z: float = DENOISE_SIGMA_Z, device: int = 0):
+        """The frame at its spp, denoised on the device: render_samples_device with the sums of squares, then
+        render_features_device, then denoise_device, on device buffers this object keeps from one call to the next
+        (torch tensors on cuda:device), default stream.  -> (mean radiance[h, w, 3] in render()'s row order, stats of
+        the colour samples)."""
+        import torch
+
+        px = self.w * self.h
+        key = (device, self.w, self.h)
+        if getattr(self, "_denoise_key", None) != key:
+            dev = torch.device("cuda", device)
+            self._denoise_bufs = (torch.empty(px * 14, dtype=torch.float32, device=dev),
+                                  torch.empty(denoise_scratch_bytes(self.w, self.h), dtype=torch.uint8, device=dev),
+                                  torch.empty(px * 3, dtype=torch.float32, device=dev))
+            self._denoise_key = key
+        sums, scratch, out = self._denoise_bufs
+        sums.zero_()
+        torch.cuda.synchronize(device)
+        b = sums.data_ptr()
+        d_sum, d_sq, d_alb, d_nrm, d_dep = (b + 4 * px * k for k in (0, 3, 6, 9, 12))
+        st = self.render_samples_device(d_sum, d_sq, device=device, want_stats=True)
+        self.render_features_device(d_alb, d_nrm, d_dep, device=device)
+        denoise_device(d_sum, d_sq, d_alb, d_nrm, d_dep, self.w, self.h, self.spp, out.data_ptr(), scratch.data_ptr(),
+                       iterations=iterations, sigma_l=sigma_l, sigma_n=sigma_n, sigma_z=sigma_z, device=device)
+        torch.cuda.synchronize(device)
+        return out.cpu().numpy().reshape(self.h, self.w, 3), st
+
+
+def denoise_scratch_bytes(w: int, h: int) -> int:
+    """rtw_denoise_scratch_bytes: the device scratch denoise_device needs for a w x h image (host only)."""
+    n = C.c_uint64()
+    _check(lib().rtw_denoise_scratch_bytes(w, h, C.byref(n)))
+    return int(n.value)
+
+
+def denoise_device(d_sum_ptr: int, d_sq_ptr: int, d_albedo_ptr: int, d_normal_ptr: int, d_depth_ptr: int, w: int,
+                   h: int, samples: int, d_out_ptr: int, d_scratch_ptr: int, d_tile_samples_ptr: int = 0,
+                   iterations: int = DENOISE_ITERATIONS, sigma_l: float = DENOISE_SIGMA_L,
+                   sigma_n: float = DENOISE_SIGMA_N, sigma_z: float = DENOISE_SIGMA_Z, device: int = -1,
+                   stream_ptr: int = 0):
+    """rtw_denoise_device: enqueue the edge-avoiding a-trous filter (include/rtw.h defines it) over full-layout device
+    sums holding `samples` samples per pixel, or tile_samples[tile] with a table: colour sums, and unless 0 the sums of
+    squares and the albedo, normal and depth sums of render_features_device -> mean radiance, 3 floats per pixel, at
+    d_out.  d_scratch: denoise_scratch_bytes(w, h) bytes, 16-byte aligned."""
+    v = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+    _check(lib().rtw_denoise_device(device, v(d_sum_ptr), v(d_sq_ptr), v(d_albedo_ptr), v(d_normal_ptr),
+                                    v(d_depth_ptr), w, h, samples, v(d_tile_samples_ptr), iterations, sigma_l, sigma_n,
+                                    sigma_z, v(d_out_ptr), v(d_scratch_ptr), C.c_void_p(stream_ptr)))
+
+
+def denoise(sums, samples: int, sq=None, albedo=None, normal=None, depth=None, tile_samples=None,
+            iterations: int = DENOISE_ITERATIONS, sigma_l: float = DENOISE_SIGMA_L, sigma_n: float = DENOISE_SIGMA_N,
+            sigma_z: float = DENOISE_SIGMA_Z) -> np.ndarray:
+    """rtw_denoise: denoise_device's arithmetic on the host, no GPU.  sums[h, w, 3] and the optional sq[h, w, 3],
+    albedo[h, w, 3], normal[h, w, 3], depth[h, w, 2] hold `samples` samples per pixel, or tile_samples[tile] with a
+    table (then `samples` may be 0) -> mean radiance[h, w, 3]."""
+    s = np.ascontiguousarray(sums, np.float32)
+    h, w = s.shape[:2]
+    opt = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (sq, albedo, normal, depth)]
+    for a, ch, name in zip(opt, (3, 3, 3, 2), ("sq", "albedo", "normal", "depth")):
+        if a is not None and a.shape != (h, w, ch):
+            raise ValueError(f"{name} has shape {a.shape}, the {w}x{h} frame wants {(h, w, ch)}")
+    ts = None if tile_samples is None else _ua(tile_samples)
+    if ts is not None and ts.size != n_tiles(w, h):
+        raise ValueError(f"tile_samples has {ts.size} entries, the {w}x{h} image {n_tiles(w, h)} tiles")
+    out = np.empty((h, w, 3), np.float32)
+    _check(lib().rtw_denoise(_fp(s), *[None if a is None else _fp(a) for a in opt], w, h, samples,
+                             None if ts is None else _up(ts), iterations, sigma_l, sigma_n, sigma_z, _fp(out)))
+    return out
+
 
 
 def tile_noise_device(d_sum_ptr: int, d_sq_ptr: int, w: int, h: int, samples: int, threshold: float, d_err_ptr: int,

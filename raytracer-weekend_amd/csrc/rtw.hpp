@@ -19,6 +19,7 @@
 //   (no counterpart: the frame in growing steps)        Raytracer(..).render_progressive(on_frame, step); sample_blocks; tonemap_device
 //   (no counterpart: a sample count per 8x8 tile)       Raytracer(..).render_adaptive(threshold, min_spp) -> AdaptiveFrame; tile_noise_device; tonemap_tiles
 //   (no counterpart: a denoiser's guides)               Raytracer(..).render_features() -> FeatureFrame; render_features_device
+//   (no counterpart: the denoiser)                       denoise_device; denoise; denoise_scratch_bytes
 // Errors (the reference panics) throw rtw::Error with rtw_last_error()'s message.
 #pragma once
 #include <stdexcept>
@@ -378,6 +379,39 @@ inline std::vector<uint8_t> tonemap_tiles(const std::vector<float>& sums, uint32
 inline void tonemap_tiles_device(const float* d_rgb_sum, uint32_t w, uint32_t h, const uint32_t* d_tile_samples,
                                  uint8_t* d_rgb8, int device = -1, void* stream = nullptr) {
   check(rtw_tonemap_tiles_device(device, d_rgb_sum, w, h, d_tile_samples, d_rgb8, stream));
+}
+
+// The denoiser (include/rtw.h defines the filter): its starting point, as the Python layer's and rtw_console's
+constexpr uint32_t DENOISE_ITERATIONS = 5;
+constexpr float DENOISE_SIGMA_L = 4.0f, DENOISE_SIGMA_N = 0.5f, DENOISE_SIGMA_Z = 0.1f;
+// the device scratch denoise_device needs for a w x h image (rtw_denoise_scratch_bytes; host only)
+inline uint64_t denoise_scratch_bytes(uint32_t w, uint32_t h) {
+  uint64_t bytes = 0;
+  check(rtw_denoise_scratch_bytes(w, h, &bytes));
+  return bytes;
+}
+// The edge-avoiding a-trous filter over full-layout device sums holding `samples` samples per pixel (or
+// d_tile_samples[tile]), enqueued on `stream` (rtw_denoise_device): colour sums and, each or nullptr, the sums of
+// squares and render_features_device's albedo, normal and depth -> mean radiance, 3 floats per pixel, at d_out
+inline void denoise_device(const float* d_sum, const float* d_sq, const float* d_albedo, const float* d_normal,
+                           const float* d_depth, uint32_t w, uint32_t h, uint32_t samples, float* d_out,
+                           void* d_scratch, const uint32_t* d_tile_samples = nullptr,
+                           uint32_t iterations = DENOISE_ITERATIONS, float sigma_l = DENOISE_SIGMA_L,
+                           float sigma_n = DENOISE_SIGMA_N, float sigma_z = DENOISE_SIGMA_Z, int device = -1,
+                           void* stream = nullptr) {
+  check(rtw_denoise_device(device, d_sum, d_sq, d_albedo, d_normal, d_depth, w, h, samples, d_tile_samples, iterations,
+                           sigma_l, sigma_n, sigma_z, d_out, d_scratch, stream));
+}
+// the same arithmetic over host arrays, no GPU (rtw_denoise) -> mean radiance, w * h * 3 floats
+inline std::vector<float> denoise(const float* sum, const float* sq, const float* albedo, const float* normal,
+                                  const float* depth, uint32_t w, uint32_t h, uint32_t samples,
+                                  const uint32_t* tile_samples = nullptr, uint32_t iterations = DENOISE_ITERATIONS,
+                                  float sigma_l = DENOISE_SIGMA_L, float sigma_n = DENOISE_SIGMA_N,
+                                  float sigma_z = DENOISE_SIGMA_Z) {
+  std::vector<float> out((size_t)w * h * 3);
+  check(rtw_denoise(sum, sq, albedo, normal, depth, w, h, samples, tile_samples, iterations, sigma_l, sigma_n, sigma_z,
+                    out.data()));
+  return out;
 }
 
 }  // namespace rtw

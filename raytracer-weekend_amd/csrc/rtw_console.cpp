@@ -2,7 +2,7 @@
 //
 //   rtw_console <scene> [-w|--width 400] [-a|--aspect-ratio 1.7777778] [-s|--samples-per-pixel 100]
 //               [--seed 0] [--models models] [--out render] [--progressive STEP] [--adaptive THRESHOLD [--min-spp 16]]
-//               [--features]
+//               [--features] [--denoise [ITERATIONS]]
 // Same Opts and defaults (main.rs:15-26), height = round(width / aspect) (:33), camera
 // aspect = width / height as f32 (:38-41), tonemap (:68-90), PNG to render/image_0000.png (:92-94).
 // --progressive (no counterpart in console_app) renders each frame through rtw_render_progressive: the PNG is rewritten
@@ -11,6 +11,9 @@
 // through rtw_tonemap_tiles: every 8x8 tile is the one-shot frame's at the sample count it stopped at.
 // --features writes, beside each frame's PNG, the denoiser's guides from rtw_render_features at the frame's spp:
 // albedo_NNNN.png (rtw_tonemap of the albedo sums) and normal_NNNN.png (the summed normal's direction, 0.5 + 0.5 n).
+// --denoise writes, beside each frame's PNG, image_NNNN_denoised.png: the frame through rtw_denoise (the edge-avoiding
+// a-trous filter of include/rtw.h on the host arrays the render calls return, rtw.hpp's default sigmas) and rtw_tonemap.
+#include <ctype.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -100,7 +103,8 @@ static void normal_rgb8(const float* n, size_t n_pixels, uint8_t* rgb) {
 int main(int argc, char** argv) {
   std::string scene, models = "models", out_dir = "render";
   uint32_t width = 400, spp = 100, step = 0, min_spp = 16;
-  bool progressive = false, adaptive = false, features = false;
+  bool progressive = false, adaptive = false, features = false, denoise = false;
+  uint32_t denoise_iterations = rtw::DENOISE_ITERATIONS;
   float threshold = 0.0f;
   double aspect = 1.7777778;
   uint64_t seed = 0;
@@ -119,12 +123,17 @@ int main(int argc, char** argv) {
     else if (a == "--progressive") { progressive = true; step = (uint32_t)atoi(next("--progressive")); }
     else if (a == "--adaptive") { adaptive = true; threshold = (float)atof(next("--adaptive")); }
     else if (a == "--features") features = true;
+    else if (a == "--denoise") {
+      denoise = true;
+      if (k + 1 < argc && isdigit((unsigned char)argv[k + 1][0])) denoise_iterations = (uint32_t)atoi(argv[++k]);
+    }
     else if (a == "--min-spp") min_spp = (uint32_t)atoi(next("--min-spp"));
     else if (a == "-h" || a == "--help") {
       printf("usage: rtw_console <jumpy-balls|two-spheres|two-perlin-spheres|earth|simple-light|cornell-box|"
              "smokey-cornell-box|book2-final-scene|animated-book2-final-scene|simple-triangle|wavefront-cow-obj|"
              "wavefront-suspension-obj|textured-monument> [-w W] [-a ASPECT] [-s SPP] [--seed N] [--models DIR] "
-             "[--out DIR] [--progressive STEP] [--adaptive THRESHOLD [--min-spp N]] [--features]\n"
+             "[--out DIR] [--progressive STEP] [--adaptive THRESHOLD [--min-spp N]] [--features] "
+             "[--denoise [ITERATIONS]]\n"
              "  --progressive STEP  render each frame in growing steps (1, 2, 4, ... samples while the doubled count is\n"
              "      within STEP, then STEP at a time; 0 = doubling to the end); after every step the frame's PNG is\n"
              "      rewritten and the samples done and the mean relative standard error are printed.  That error, from\n"
@@ -139,12 +148,17 @@ int main(int argc, char** argv) {
              "      number of tiles per sample count.\n"
              "  --features  also write the denoiser's guides of each frame, first-hit features summed over the pixel's\n"
              "      SPP camera rays: albedo_NNNN.png (the albedo sums through the image's tonemap) and normal_NNNN.png\n"
-             "      (per channel 255.999 clamp(0.5 + 0.5 N_c / |N|, 0, 0.999) of the summed normal N; 0.5 where N = 0).\n");
+             "      (per channel 255.999 clamp(0.5 + 0.5 N_c / |N|, 0, 0.999) of the summed normal N; 0.5 where N = 0).\n"
+             "  --denoise [ITERATIONS]  also write image_NNNN_denoised.png: the frame's sums, sums of squares and guides\n"
+             "      through the edge-avoiding a-trous filter (rtw.h; ITERATIONS passes, default 5, at most 10; sigma_l 4,\n"
+             "      sigma_n 0.5, sigma_z 0.1), on the host arrays the render calls return.  Meant for few samples (-s 4).\n"
+             "      Not with --adaptive.\n");
       return 0;
     } else if (scene.empty()) scene = a;
     else { fprintf(stderr, "unexpected argument '%s'\n", a.c_str()); return 2; }
   }
   if (scene.empty()) { fprintf(stderr, "missing scene subcommand (try --help)\n"); return 2; }
+  if (denoise && adaptive) { fprintf(stderr, "--denoise is not combined with --adaptive\n"); return 2; }
   const uint32_t height = (uint32_t)llround((double)width / aspect);  // main.rs:33 (f64 round)
   try {
     rtw::World world;
@@ -162,16 +176,24 @@ int main(int argc, char** argv) {
       snprintf(name, sizeof name, "/image_%04zu.png", frame);  // main.rs:92-94
       std::string path = out_dir + name;
       std::vector<uint8_t> img((size_t)width * height * 3);
-      if (progressive) {
+      std::vector<float> dn_sum, dn_sq;  // --denoise: the finished frame's sums and sums of squares
+      if (progressive || denoise) {  // (--denoise alone: the progressive call for its squares; only the last step is written)
+        const size_t n3 = (size_t)width * height * 3;
         const int rc = rt.render_progressive([&](const float* sum, const float* sq, uint32_t done) {
+          if (denoise && done == spp) {
+            dn_sum.assign(sum, sum + n3);
+            dn_sq.assign(sq, sq + n3);
+          }
+          if (!progressive && done != spp) return 0;
           if (rtw_tonemap(sum, width * height, done, img.data()) != RTW_OK) return 1;  // (nothing throws through C)
           if (!write_png(path.c_str(), img.data(), width, height)) return 1;
+          if (!progressive) return 0;
           if (done > 1) printf("  %u spp: mean relative standard error %.4f\n", done,
                                mean_rel_stderr(sum, sq, (size_t)width * height, done));
           else printf("  %u spp: mean relative standard error n/a\n", done);
           fflush(stdout);
           return 0;
-        }, step, &st);
+        }, progressive ? step : 0, &st);
         if (rc) { fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
       } else if (adaptive) {
         const rtw::AdaptiveFrame fr = rt.render_adaptive(threshold, std::min(min_spp, spp), &st);
@@ -185,8 +207,17 @@ int main(int argc, char** argv) {
         rtw::check(rtw_tonemap(sums.data(), width * height, spp, img.data()));
         if (!write_png(path.c_str(), img.data(), width, height)) { fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
       }
+      rtw::FeatureFrame ff;
+      if (features || denoise) ff = rt.render_features();
+      if (denoise) {
+        const std::vector<float> mean = rtw::denoise(dn_sum.data(), dn_sq.data(), ff.albedo.data(), ff.normal.data(),
+                                                     ff.depth.data(), width, height, spp, nullptr, denoise_iterations);
+        snprintf(name, sizeof name, "/image_%04zu_denoised.png", frame);
+        const std::string dpath = out_dir + name;
+        rtw::check(rtw_tonemap(mean.data(), width * height, 1, img.data()));
+        if (!write_png(dpath.c_str(), img.data(), width, height)) { fprintf(stderr, "cannot write %s\n", dpath.c_str()); return 1; }
+      }
       if (features) {
-        const rtw::FeatureFrame ff = rt.render_features();
         snprintf(name, sizeof name, "/albedo_%04zu.png", frame);
         const std::string apath = out_dir + name;
         rtw::check(rtw_tonemap(ff.albedo.data(), width * height, spp, img.data()));

@@ -2,7 +2,7 @@
 // that are no templates (reduce_kernel, unpack_tiles_kernel, tile_list_kernel with its diagnostic calls, the libm and
 // reciprocal diagnostics, with the two calls that launch the latter), the tuning knobs, pick_kernel (which path-kernel variant a scene runs) and the launches
 // (enqueue_render, enqueue_render_samples, enqueue_tonemap, enqueue_tile_noise, enqueue_tonemap_tiles, enqueue_hit_rays,
-// enqueue_sample_rays, enqueue_scatter_rays, enqueue_camera_rays, enqueue_features, enqueue_unpack),
+// enqueue_sample_rays, enqueue_scatter_rays, enqueue_camera_rays, enqueue_features, enqueue_denoise, enqueue_unpack),
 // which share one cache of resident grids (resident_blocks), the walk's tuning (tune_walk) and the one-record-per-lane
 // queries' launch (launch_query).  The
 // scene's device copies, statistics and the render entry points are plain HIP runtime code in rtw_render.cpp, the
@@ -50,6 +50,8 @@
 // Adaptive renders (rtw_tile_noise_device, rtw_render_adaptive*): tile_noise_kernel and compact_tiles_kernel of the same
 // header turn the two sums into the ids of the tiles still above the threshold (enqueue_tile_noise); the loop around
 // enqueue_render_samples and it is rtw_render.cpp's.
+// The denoiser (rtw_denoise_device): rtw_denoise_kernel.hpp's prepare, a-trous and finish kernels over the film's sums
+// and the feature buffers, enqueue_denoise; no scene, no device copy.
 // Variants: path_kernel<COUNT, KernelCfg K> -- one plain aggregate (stack rows, spill, waves / SIMD, feature set,
 // workgroup size, LDS node table, half nodes, 16-bit stack) is the template argument, defines every property derived
 // from it, and travels with the kernel to the host (Variant, rtw_variants.hpp), which sizes the launch from it.
@@ -71,6 +73,7 @@
 #include "rtw_variants.hpp"
 #include "rtw_shade_kernel.hpp"
 #include "rtw_film_kernel.hpp"
+#include "rtw_denoise_kernel.hpp"
 #include "rtw_tile_beam.h"
 
 namespace rtw {
@@ -771,6 +774,56 @@ int enqueue_tonemap_tiles(const float* d_sum, uint32_t w, uint32_t h, const uint
   hipLaunchKernelGGL(dev::tonemap_tiles_kernel, dim3(grid), dim3(dev::FILM_BLOCK), 0, stream, d_sum, w, h,
                      (w + 7u) / 8u, d_tile_samples, d_rgb8);
   HIPCHK(hipGetLastError(), "tonemap_tiles_kernel launch");
+  return RTW_OK;
+}
+
+// The denoiser's launches: the prepare, `iterations` a-trous passes that ping-pong between the scratch's two record
+// images (the last one writes d_out: the finish is fused into it), or prepare and finish alone for iterations = 0.
+// Scratch layout, DENOISE_SCRATCH_PER_PIXEL = 64 bytes per pixel: X, Y, G, D images of one float4 each.
+// Which steps take their taps through LDS: DENOISE_LDS_STEPS, bit k = the iteration of step 1 << k, measured on an
+// MI355X at 1920x1080 (Denoiser); steps from 4 up read global memory.  Tuning knob
+// RTW_DENOISE_LDS (a mask of bits 0-2) for the A/B.
+constexpr uint32_t DENOISE_LDS_STEPS = 0x3u;
+int enqueue_denoise(const float* d_sum, const float* d_sq, const float* d_albedo, const float* d_normal,
+                    const float* d_depth, uint32_t w, uint32_t h, uint32_t samples, const uint32_t* d_tile_samples,
+                    uint32_t iterations, float sigma_l, float sigma_n, float sigma_z, float* d_out, void* d_scratch,
+                    hipStream_t stream) {
+  using namespace dev;
+  const char* e = tuning_env("RTW_DENOISE_LDS");
+  const uint32_t lds_steps = e ? ((uint32_t)atoi(e) & 0x7u) : DENOISE_LDS_STEPS;
+  const size_t px = (size_t)w * h;
+  float4* base = static_cast<float4*>(d_scratch);
+  DenoiseArgs a;
+  memset(&a, 0, sizeof a);
+  a.sum = d_sum; a.sq = d_sq; a.albedo = d_albedo; a.normal = d_normal; a.depth = d_depth;
+  a.tile_samples = d_tile_samples;
+  a.w = w; a.h = h; a.tiles_x = (w + 7u) / 8u; a.samples = samples;
+  a.X = base; a.Y = base + px; a.G = base + 2 * px; a.D = base + 3 * px;
+  a.out = d_out;
+  a.k_n = sigma_n != 0.0f ? 1.0f / (sigma_n * sigma_n) : 0.0f;
+  a.sigma_l = sigma_l;
+  a.use_n = sigma_n != 0.0f; a.use_z = sigma_z != 0.0f; a.use_l = sigma_l != 0.0f && d_sq != nullptr;
+  const dim3 grid((w + DENOISE_TX - 1u) / DENOISE_TX, (h + DENOISE_TY - 1u) / DENOISE_TY), block(DENOISE_BLOCK);
+  hipLaunchKernelGGL(denoise_prepare_kernel, grid, block, 0, stream, a);
+  HIPCHK(hipGetLastError(), "denoise_prepare_kernel launch");
+  if (iterations == 0) {
+    hipLaunchKernelGGL(denoise_finish_kernel, grid, block, 0, stream, a);
+    HIPCHK(hipGetLastError(), "denoise_finish_kernel launch");
+    return RTW_OK;
+  }
+  for (uint32_t k = 0; k < iterations; ++k) {
+    a.step = 1u << k;
+    a.sz_step = sigma_z * (float)a.step;
+    const bool lds = k < 3u && (lds_steps >> k & 1u), fin = k + 1u == iterations;
+    const uint32_t lw = DENOISE_TX + 4u * a.step, lh = DENOISE_TY + 4u * a.step;
+    const size_t lds_bytes = lds ? (size_t)lw * lh * 2u * sizeof(float4) : 0;
+    if (lds && fin) hipLaunchKernelGGL((denoise_atrous_kernel<true, true>), grid, block, lds_bytes, stream, a);
+    else if (lds) hipLaunchKernelGGL((denoise_atrous_kernel<true, false>), grid, block, lds_bytes, stream, a);
+    else if (fin) hipLaunchKernelGGL((denoise_atrous_kernel<false, true>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((denoise_atrous_kernel<false, false>), grid, block, 0, stream, a);
+    HIPCHK(hipGetLastError(), "denoise_atrous_kernel launch");
+    std::swap(a.X, a.Y);
+  }
   return RTW_OK;
 }
 

@@ -288,6 +288,14 @@ int enqueue_tile_noise(const float* d_sum, const float* d_sq, uint32_t w, uint32
 // enqueue rtw_tonemap_tiles over device arrays on `stream` of the current device
 int enqueue_tonemap_tiles(const float* d_sum, uint32_t w, uint32_t h, const uint32_t* d_tile_samples, uint8_t* d_rgb8,
                           hipStream_t stream);
+// enqueue rtw_denoise over device arrays on `stream` of the current device: the prepare kernel, `iterations` a-trous
+// passes and the finish.  d_scratch holds DENOISE_SCRATCH_PER_PIXEL bytes per pixel, 16-byte aligned.  The caller has
+// checked the arguments (rtw_denoise_device).
+constexpr uint64_t DENOISE_SCRATCH_PER_PIXEL = 64;
+int enqueue_denoise(const float* d_sum, const float* d_sq, const float* d_albedo, const float* d_normal,
+                    const float* d_depth, uint32_t w, uint32_t h, uint32_t samples, const uint32_t* d_tile_samples,
+                    uint32_t iterations, float sigma_l, float sigma_n, float sigma_z, float* d_out, void* d_scratch,
+                    hipStream_t stream);
 // enqueue one closest-hit query of n rays (rtw_ray[n] -> rtw_hit[n], device arrays) on `stream` of c.device, which
 // must be current; ev0 / ev1 (or NULL) are recorded around the kernel
 int enqueue_hit_rays(Scene& s, DeviceCopy& c, uint64_t n, const void* d_rays, void* d_hits, hipStream_t stream,
