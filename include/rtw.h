@@ -430,6 +430,89 @@ int rtw_denoise(const float* rgb_sum, const float* rgb_sq_sum, const float* albe
                 const float* depth, uint32_t w, uint32_t h, uint32_t samples, const uint32_t* tile_samples,
                 uint32_t iterations, float sigma_l, float sigma_n, float sigma_z, float* out);
 
+/* ---- temporal accumulation: the previous frames' accumulated sums, reprojected onto the next camera and added to
+ *      the new frame's, so that a sequence of few-sample frames gathers samples over time (SVGF's other half beside
+ *      the filter above).  A frame stays what it is everywhere in this library, sums plus counts.  The world is the
+ *      same for both frames: motion here lives inside the shutter, so a committed scene is static from frame to frame.
+ *      No counterpart in the reference, so the operation is DEFINED here, operation by operation: all arithmetic f32
+ *      with one rounding per operation (no fused multiply-add), IEEE division, sqrt and floorf, no transcendentals;
+ *      dot(a, b) = (a_0 b_0 + a_1 b_1) + a_2 b_2.  The device kernel, rtw_temporal's host loops and the tests' numpy
+ *      restatement agree bit for bit.
+ *      An ACCUMULATED FRAME is six full-layout w x h buffers, rows as rtw_render: sum (3 floats per pixel), sq (3),
+ *      albedo (3), normal (3), depth (2: the sums of t and of hits), as the render calls leave them, and count
+ *      (1 float): the effective samples the other five hold.  A fresh render of n samples is an accumulated frame with
+ *      count = (float)n.
+ *      Inputs: the CURRENT frame's five sums with `samples` or a tile table (n as for the denoiser) and its camera;
+ *      the HISTORY, an accumulated frame and the camera it was rendered with (primed below).  O, llc, H, V, w are a
+ *      camera's origin, lower_left_corner, horizontal, vertical and w.
+ *      Per pixel p = (i, row), j = h - 1 - row.  "Copy" means: every output is the current value and out_count = c.
+ *       1. n = 0: every output, out_count too, is +0.  Otherwise c = (float)n.
+ *       2. Copy without a history (hist_count NULL).
+ *       3. hits = D_1 (the current depth's second channel).  Copy unless hits > 0.  tbar = D_0 / hits.
+ *       4. The world point through the pixel's centre at that depth (the lens offset is ignored: its mean is zero):
+ *            s = ((float)i + 0.5f) / (float)(w - 1);  v = ((float)j + 0.5f) / (float)(h - 1);
+ *            d_k = ((llc_k + s * H_k) + v * V_k) - O_k;  P_k = O_k + tbar * d_k.
+ *       5. Into the history camera:  r_k = P_k - O'_k;  e_k = llc'_k - O'_k;
+ *            tau = dot(r, w') / dot(e, w')              (the depth the point would have had in the history frame);
+ *            s' = (dot(r, H') / tau - dot(e, H')) / dot(H', H');  v' = (dot(r, V') / tau - dot(e, V')) / dot(V', V');
+ *            x = s' * (float)(w - 1) - 0.5f;  y = (float)(h - 1) - (v' * (float)(h - 1) - 0.5f).
+ *          Copy unless tau > 0 && x >= -1 && x < (float)w && y >= -1 && y < (float)h (a NaN fails; tested on the floats,
+ *          before any conversion to an integer).
+ *       6. x0 = floorf(x), fx = x - x0, gx = 1.0f - fx; y0, fy, gy likewise.  Four taps q, in the order (y0, x0),
+ *          (y0, x0 + 1), (y0 + 1, x0), (y0 + 1, x0 + 1), with the weights b = gx * gy, fx * gy, gx * fy, fx * fy.
+ *          A tap counts iff all of these hold, tested in this order: it is on the image; b > 0; L_q = hist_count[q] > 0;
+ *          hq = hist_depth[q]_1 > 0; with zq = hist_depth[q]_0 / hq, fabsf(tau - zq) <= tol_z * tau; with normals
+ *          given, dot(g_p, g_q) >= cos_n, g the unit normal of the current / the history normal sum as the denoiser's
+ *          prepare makes it (nn = dot(N, N); g_k = nn > 0 ? N_k / sqrtf(nn) : +0); its colour sum is finite:
+ *          t = (S_q0 + S_q1) + S_q2, t - t == 0.  Then sb = sb + b, sL = sL + b * L_q and, for every channel of every
+ *          buffer in use, sX = sX + b * X_q, all starting at +0, in tap order: the order is the contract.
+ *       7. Copy unless sb > 0.  Otherwise Lr = sL / sb;  lam = Lr > max_history ? max_history / Lr : 1.0f;
+ *          k = lam / sb;  every output channel is X_cur + k * sX, and out_count = c + k * sL.
+ *      So the history enters with at most max_history effective samples (an exponential average once it is reached),
+ *      and a pixel the history cannot vouch for -- off the old frame, behind the old camera, disoccluded (the depth
+ *      test), on another surface (the normal test) -- starts afresh.  What the definition ignores: the lens offset,
+ *      view-dependent shading (a highlight is reprojected as if it stuck to its surface) and geometry that moves.
+ *      Buffers: sum, depth, cam, out_sum, out_depth and out_count are required.  sq, albedo and normal are optional
+ *      triples (current, history, out): current and out are both given or both NULL, and when they are NULL the
+ *      history's is ignored.  hist_count NULL means no history; every other hist pointer and hist_cam are then ignored.
+ *      With a history, hist_sum, hist_depth and hist_cam are required, and so is the hist buffer of each triple in use.
+ *      An out buffer may be its own current-frame buffer (in place: a pixel reads only its own current values); it may
+ *      never be a history buffer, because the call gathers.
+ *      Both calls answer RTW_EINVAL for, in this order: a NULL sum, depth, cam, out_sum, out_depth or out_count; a
+ *      triple (sq, albedo, normal in turn) given on one side only; with a history, a NULL hist_sum, hist_depth or
+ *      hist_cam, then a NULL hist buffer of a triple in use (sq, albedo, normal in turn); with a history, an out buffer
+ *      that is a history buffer (equal addresses); an image under 2x2 or over 65536 a side; samples = 0 without a tile
+ *      table; max_history NaN, negative or infinite (0 is valid: the history never contributes); tol_z NaN, negative
+ *      or infinite; cos_n NaN or outside [-1, 1]. */
+/* The pass over DEVICE arrays, enqueued on `stream` (no scene, no scratch: what rtw_tonemap_device is to rtw_tonemap).
+ * device < 0 means the current device.  Nothing is written beyond the six out buffers' w*h*(3, 3, 3, 3, 2, 1) floats. */
+int rtw_temporal_device(int device, const float* d_sum, const float* d_sq, const float* d_albedo, const float* d_normal,
+                        const float* d_depth, uint32_t w, uint32_t h, uint32_t samples, const uint32_t* d_tile_samples,
+                        const rtw_camera* cam, const float* d_hist_sum, const float* d_hist_sq,
+                        const float* d_hist_albedo, const float* d_hist_normal, const float* d_hist_depth,
+                        const float* d_hist_count, const rtw_camera* hist_cam, float max_history, float tol_z,
+                        float cos_n, float* d_out_sum, float* d_out_sq, float* d_out_albedo, float* d_out_normal,
+                        float* d_out_depth, float* d_out_count, void* stream);
+/* The same arithmetic as plain loops over HOST arrays, no GPU. */
+int rtw_temporal(const float* rgb_sum, const float* rgb_sq_sum, const float* albedo, const float* normal,
+                 const float* depth, uint32_t w, uint32_t h, uint32_t samples, const uint32_t* tile_samples,
+                 const rtw_camera* cam, const float* hist_sum, const float* hist_sq, const float* hist_albedo,
+                 const float* hist_normal, const float* hist_depth, const float* hist_count,
+                 const rtw_camera* hist_cam, float max_history, float tol_z, float cos_n, float* out_sum,
+                 float* out_sq, float* out_albedo, float* out_normal, float* out_depth, float* out_count);
+/* The denoiser above for an accumulated frame, whose sample count differs per pixel: one change in its prepare.  A
+ * pixel's n is count[p] (1 float per pixel); the pixel is empty unless count > 0 (a NaN is empty), and
+ * inv = 1.0f / count.  Everything after that is the denoiser's definition, through the same kernels; the same scratch
+ * (rtw_denoise_scratch_bytes) and the same checks in the same order, with count among the buffers of the first check
+ * and without the one on samples. */
+int rtw_denoise_counts_device(int device, const float* d_sum, const float* d_sq, const float* d_albedo,
+                              const float* d_normal, const float* d_depth, const float* d_count, uint32_t w,
+                              uint32_t h, uint32_t iterations, float sigma_l, float sigma_n, float sigma_z,
+                              float* d_out, void* d_scratch, void* stream);
+int rtw_denoise_counts(const float* rgb_sum, const float* rgb_sq_sum, const float* albedo, const float* normal,
+                       const float* depth, const float* count, uint32_t w, uint32_t h, uint32_t iterations,
+                       float sigma_l, float sigma_n, float sigma_z, float* out);
+
 /* ---- closest-hit ray queries: Hittable::hit(&ray, t_min, t_max) -> Option<HitRecord> on the world list
  *      (hittable/mod.rs:22-69) for rays the caller chooses.  A query is world.hit(ray, 0.001, +inf), the interval of
  *      lib.rs:102 and the only one the render's culling is proven for: t_min and t_max are not parameters.  The winner

@@ -190,6 +190,15 @@ _SIGS = {
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtw_denoise": (C.c_int, [_F, _F, _F, _F, _F, C.c_uint32, C.c_uint32, C.c_uint32, _U32, C.c_uint32, C.c_float,
                               C.c_float, C.c_float, _F]),
+    "rtw_temporal_device": (C.c_int, [C.c_int] + [C.c_void_p] * 5 + [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                      C.POINTER(rtw_camera)] + [C.c_void_p] * 6 + [C.POINTER(rtw_camera), C.c_float,
+                                      C.c_float, C.c_float] + [C.c_void_p] * 7),
+    "rtw_temporal": (C.c_int, [_F] * 5 + [C.c_uint32, C.c_uint32, C.c_uint32, _U32, C.POINTER(rtw_camera)] + [_F] * 6 +
+                               [C.POINTER(rtw_camera), C.c_float, C.c_float, C.c_float] + [_F] * 6),
+    "rtw_denoise_counts_device": (C.c_int, [C.c_int] + [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.c_uint32, C.c_float,
+                                            C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtw_denoise_counts": (C.c_int, [_F] * 6 + [C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float,
+                                     _F]),
     "rtw_hit_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(rtw_ray), C.POINTER(rtw_hit),
                                C.POINTER(rtw_stats)]),
     "rtw_hit_rays_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -249,6 +258,10 @@ ABI_VERSION = 7  # include/rtw.h RTW_ABI_VERSION
 # the denoiser's starting point (denoise, denoise_device, Raytracer.render_denoised; rtw.hpp and rtw_console use the
 # same): DESIGN.md "Denoiser" has the error ratios they give
 DENOISE_ITERATIONS, DENOISE_SIGMA_L, DENOISE_SIGMA_N, DENOISE_SIGMA_Z = 5, 4.0, 0.5, 0.1
+# temporal accumulation's starting point (temporal, temporal_device, TemporalRenderer; rtw.hpp and rtw_console use the
+# same), not a tuned result: the history is capped at max_history = TEMPORAL_MAX_HISTORY_FRAMES * spp effective samples,
+# a tap's depth may differ by TEMPORAL_TOL_Z of the reprojected depth, and its normal by arccos(TEMPORAL_COS_N)
+TEMPORAL_MAX_HISTORY_FRAMES, TEMPORAL_TOL_Z, TEMPORAL_COS_N = 32, 0.05, 0.9
 
 
 def lib_sha() -> str:
@@ -896,6 +909,167 @@ def denoise(sums, samples: int, sq=None, albedo=None, normal=None, depth=None, t
     _check(lib().rtw_denoise(_fp(s), *[None if a is None else _fp(a) for a in opt], w, h, samples,
                              None if ts is None else _up(ts), iterations, sigma_l, sigma_n, sigma_z, _fp(out)))
     return out
+
+
+_FRAME_KEYS = ("sum", "sq", "albedo", "normal", "depth")  # an accumulated frame's buffers before its count
+_FRAME_CH = {"sum": 3, "sq": 3, "albedo": 3, "normal": 3, "depth": 2, "count": 1}
+
+
+def temporal_device(cur: dict, w: int, h: int, samples: int, cam: "Camera", out: dict, hist=None, hist_cam=None,
+                    max_history=None, tol_z: float = TEMPORAL_TOL_Z, cos_n: float = TEMPORAL_COS_N,
+                    d_tile_samples_ptr: int = 0, device: int = -1, stream_ptr: int = 0):
+    """rtw_temporal_device: enqueue temporal accumulation (include/rtw.h defines it).  cur, hist and out map "sum", "sq",
+    "albedo", "normal", "depth" (hist and out: and "count") to device addresses of full-layout buffers; a missing key or
+    0 is NULL.  The current frame holds `samples` samples per pixel (or tile_samples[tile]) and was rendered with `cam`;
+    hist (or None: no history) is an accumulated frame rendered with hist_cam, reprojected onto cam and added with at
+    most max_history effective samples (None: TEMPORAL_MAX_HISTORY_FRAMES * samples).  An out buffer may be its
+    current-frame buffer, never a history buffer."""
+    v = lambda d, k: C.c_void_p(d[k]) if d and d.get(k) else None  # noqa: E731
+    if max_history is None:
+        max_history = float(TEMPORAL_MAX_HISTORY_FRAMES * samples)
+    _check(lib().rtw_temporal_device(
+        device, *[v(cur, k) for k in _FRAME_KEYS], w, h, samples, C.c_void_p(d_tile_samples_ptr) if d_tile_samples_ptr
+        else None, C.byref(cam.c), *[v(hist, k) for k in _FRAME_KEYS + ("count",)],
+        C.byref(hist_cam.c) if hist_cam is not None else None, max_history, tol_z, cos_n,
+        *[v(out, k) for k in _FRAME_KEYS + ("count",)], C.c_void_p(stream_ptr)))
+
+
+def temporal(cur: dict, samples: int, cam: "Camera", hist=None, hist_cam=None, max_history=None,
+             tol_z: float = TEMPORAL_TOL_Z, cos_n: float = TEMPORAL_COS_N, tile_samples=None, in_place: bool = False):
+    """rtw_temporal: temporal_device's arithmetic on the host, no GPU.  cur maps "sum"[h, w, 3], "depth"[h, w, 2] and
+    optionally "sq", "albedo", "normal"[h, w, 3] to the current frame's sums (a key missing or None: NULL); hist (or
+    None) is an accumulated frame with the same keys and "count"[h, w].  -> the accumulated frame, a dict of the keys
+    in use and "count"; in_place writes each output over its current-frame array (C-contiguous float32) and returns
+    those."""
+    if in_place:
+        c = {k: a for k, a in cur.items() if a is not None}
+        if any(a.dtype != np.float32 or not a.flags.c_contiguous or not a.flags.writeable for a in c.values()):
+            raise ValueError("in_place wants writable C-contiguous float32 arrays")
+    else:
+        c = {k: np.ascontiguousarray(a, np.float32) for k, a in cur.items() if a is not None}
+    h, w = c["sum"].shape[:2]
+    hs = None if hist is None else {k: np.ascontiguousarray(a, np.float32) for k, a in hist.items() if a is not None}
+    for d, keys in ((c, _FRAME_KEYS), (hs or {}, _FRAME_KEYS + ("count",))):
+        for k, a in d.items():
+            want = (h, w) if k == "count" else (h, w, _FRAME_CH[k])
+            if k not in keys or a.shape != want:
+                raise ValueError(f"{k} has shape {a.shape}, the {w}x{h} frame wants {want}")
+    ts = None if tile_samples is None else _ua(tile_samples)
+    if ts is not None and ts.size != n_tiles(w, h):
+        raise ValueError(f"tile_samples has {ts.size} entries, the {w}x{h} image {n_tiles(w, h)} tiles")
+    out = {k: (a if in_place else np.empty_like(a)) for k, a in c.items()}
+    out["count"] = np.empty((h, w), np.float32)
+    if max_history is None:
+        max_history = float(TEMPORAL_MAX_HISTORY_FRAMES * samples)
+    p = lambda d, k: _fp(d[k]) if d and k in d else None  # noqa: E731
+    _check(lib().rtw_temporal(
+        *[p(c, k) for k in _FRAME_KEYS], w, h, samples, None if ts is None else _up(ts), C.byref(cam.c),
+        *[p(hs, k) for k in _FRAME_KEYS + ("count",)], C.byref(hist_cam.c) if hist_cam is not None else None,
+        max_history, tol_z, cos_n, *[p(out, k) for k in _FRAME_KEYS + ("count",)]))
+    return out
+
+
+def denoise_counts_device(d_sum_ptr: int, d_sq_ptr: int, d_albedo_ptr: int, d_normal_ptr: int, d_depth_ptr: int,
+                          d_count_ptr: int, w: int, h: int, d_out_ptr: int, d_scratch_ptr: int,
+                          iterations: int = DENOISE_ITERATIONS, sigma_l: float = DENOISE_SIGMA_L,
+                          sigma_n: float = DENOISE_SIGMA_N, sigma_z: float = DENOISE_SIGMA_Z, device: int = -1,
+                          stream_ptr: int = 0):
+    """rtw_denoise_counts_device: denoise_device for an accumulated frame, whose sample count is d_count's float per
+    pixel (temporal_device's out "count"); a pixel is empty unless its count is > 0.  Scratch as denoise_device's."""
+    v = lambda p: C.c_void_p(p) if p else None  # noqa: E731
+    _check(lib().rtw_denoise_counts_device(device, v(d_sum_ptr), v(d_sq_ptr), v(d_albedo_ptr), v(d_normal_ptr),
+                                           v(d_depth_ptr), v(d_count_ptr), w, h, iterations, sigma_l, sigma_n, sigma_z,
+                                           v(d_out_ptr), v(d_scratch_ptr), C.c_void_p(stream_ptr)))
+
+
+def denoise_counts(sums, count, sq=None, albedo=None, normal=None, depth=None, iterations: int = DENOISE_ITERATIONS,
+                   sigma_l: float = DENOISE_SIGMA_L, sigma_n: float = DENOISE_SIGMA_N,
+                   sigma_z: float = DENOISE_SIGMA_Z) -> np.ndarray:
+    """rtw_denoise_counts: denoise_counts_device's arithmetic on the host, no GPU.  count[h, w] holds each pixel's
+    sample count -> mean radiance[h, w, 3]."""
+    s = np.ascontiguousarray(sums, np.float32)
+    h, w = s.shape[:2]
+    cnt = np.ascontiguousarray(count, np.float32)
+    if cnt.shape != (h, w):
+        raise ValueError(f"count has shape {cnt.shape}, the {w}x{h} frame wants {(h, w)}")
+    opt = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (sq, albedo, normal, depth)]
+    for a, ch, name in zip(opt, (3, 3, 3, 2), ("sq", "albedo", "normal", "depth")):
+        if a is not None and a.shape != (h, w, ch):
+            raise ValueError(f"{name} has shape {a.shape}, the {w}x{h} frame wants {(h, w, ch)}")
+    out = np.empty((h, w, 3), np.float32)
+    _check(lib().rtw_denoise_counts(_fp(s), *[None if a is None else _fp(a) for a in opt], _fp(cnt), w, h, iterations,
+                                    sigma_l, sigma_n, sigma_z, _fp(out)))
+    return out
+
+
+class TemporalRenderer:
+    """A sequence of few-sample frames over one committed scene, each accumulated onto the reprojected history of the
+    frames before it and denoised, all on the device.  frame(cam) renders frame k = 0, 1, ... with seed + k: the
+    generator is keyed by (seed, j, i, sample), so one seed for every frame would repeat each pixel's noise from frame
+    to frame -- screen-locked noise, correlated with the history it is averaged with, which would then be worthless.
+    Per frame: render_samples_device with the squares plus render_features_device into one of two device buffer sets
+    (torch tensors on cuda:device), temporal_device in place against the other set, then denoise_counts_device.
+    reset() drops the history: the next frame stands alone (its seed still advances)."""
+
+    def __init__(self, scene: Scene, background, image_width: int, image_height: int, samples_per_pixel: int,
+                 seed: int = 0, max_depth: int = 50, device: int = 0):
+        self.scene, self.bg = scene, _fa(background)
+        self.w, self.h, self.spp = int(image_width), int(image_height), int(samples_per_pixel)
+        self.seed, self.max_depth, self.device = int(seed), int(max_depth), int(device)
+        self.k = 0
+        self._hist_cam = None
+        self._bufs = None
+
+    def reset(self) -> None:
+        self._hist_cam = None
+
+    def _ptrs(self, t) -> dict:
+        px, b = self.w * self.h, t.data_ptr()
+        return {k: b + 4 * px * o for k, o in zip(_FRAME_KEYS + ("count",), (0, 3, 6, 9, 12, 14))}
+
+    def frame(self, cam: Camera, denoise: bool = True, max_history=None, tol_z: float = TEMPORAL_TOL_Z,
+              cos_n: float = TEMPORAL_COS_N, iterations: int = DENOISE_ITERATIONS, sigma_l: float = DENOISE_SIGMA_L,
+              sigma_n: float = DENOISE_SIGMA_N, sigma_z: float = DENOISE_SIGMA_Z):
+        """-> (mean radiance[h, w, 3] in render()'s row order, stats of the colour samples with "frame": k,
+        "history": whether one was used, and "count": the accumulated frame's effective samples[h, w]).  denoise=False
+        returns the accumulated frame's own mean, sum / count (+0 where the count is 0)."""
+        import torch
+
+        px, dev = self.w * self.h, self.device
+        if self._bufs is None:
+            td = torch.device("cuda", dev)
+            self._bufs = ([torch.empty(px * 15, dtype=torch.float32, device=td) for _ in range(2)],
+                          torch.empty(denoise_scratch_bytes(self.w, self.h), dtype=torch.uint8, device=td),
+                          torch.empty(px * 3, dtype=torch.float32, device=td))
+        sets, scratch, out = self._bufs
+        cur_t, hist_t = sets[self.k & 1], sets[(self.k & 1) ^ 1]
+        cur, hist = self._ptrs(cur_t), self._ptrs(hist_t)
+        cur_t.zero_()
+        torch.cuda.synchronize(dev)
+        rt = Raytracer(self.scene, cam, self.bg, self.w, self.h, self.spp, seed=self.seed + self.k,
+                       max_depth=self.max_depth)
+        st = rt.render_samples_device(cur["sum"], cur["sq"], device=dev, want_stats=True)
+        rt.render_features_device(cur["albedo"], cur["normal"], cur["depth"], device=dev)
+        used = self._hist_cam is not None
+        temporal_device(cur, self.w, self.h, self.spp, cam, cur, hist if used else None, self._hist_cam,
+                        max_history=max_history, tol_z=tol_z, cos_n=cos_n, device=dev)
+        if denoise:
+            denoise_counts_device(*[cur[k] for k in _FRAME_KEYS + ("count",)], self.w, self.h, out.data_ptr(),
+                                  scratch.data_ptr(), iterations=iterations, sigma_l=sigma_l, sigma_n=sigma_n,
+                                  sigma_z=sigma_z, device=dev)
+        torch.cuda.synchronize(dev)
+        acc = cur_t.cpu().numpy()
+        count = acc[14 * px:].reshape(self.h, self.w)
+        if denoise:
+            mean = out.cpu().numpy().reshape(self.h, self.w, 3)
+        else:
+            with np.errstate(all="ignore"):
+                mean = np.where(count[..., None] > 0, acc[:3 * px].reshape(self.h, self.w, 3) / count[..., None],
+                                np.float32(0.0)).astype(np.float32)
+        st.update(frame=self.k, history=used, count=count.copy())
+        self._hist_cam = Camera(rtw_camera.from_buffer_copy(cam.c))
+        self.k += 1
+        return mean, st
 
 
 

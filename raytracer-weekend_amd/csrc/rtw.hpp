@@ -20,6 +20,7 @@
 //   (no counterpart: a sample count per 8x8 tile)       Raytracer(..).render_adaptive(threshold, min_spp) -> AdaptiveFrame; tile_noise_device; tonemap_tiles
 //   (no counterpart: a denoiser's guides)               Raytracer(..).render_features() -> FeatureFrame; render_features_device
 //   (no counterpart: the denoiser)                       denoise_device; denoise; denoise_scratch_bytes
+//   (no counterpart: temporal accumulation)              temporal_device; temporal; denoise_counts_device; denoise_counts
 // Errors (the reference panics) throw rtw::Error with rtw_last_error()'s message.
 #pragma once
 #include <stdexcept>
@@ -411,6 +412,80 @@ inline std::vector<float> denoise(const float* sum, const float* sq, const float
   std::vector<float> out((size_t)w * h * 3);
   check(rtw_denoise(sum, sq, albedo, normal, depth, w, h, samples, tile_samples, iterations, sigma_l, sigma_n, sigma_z,
                     out.data()));
+  return out;
+}
+
+// Temporal accumulation (include/rtw.h defines the operation): its starting point, as the Python layer's and
+// rtw_console's, not a tuned result.  max_history = TEMPORAL_MAX_HISTORY_FRAMES * spp.
+constexpr uint32_t TEMPORAL_MAX_HISTORY_FRAMES = 32;
+constexpr float TEMPORAL_TOL_Z = 0.05f, TEMPORAL_COS_N = 0.9f;
+// An accumulated frame's buffers, device or host alike: sum, sq, albedo, normal (3 floats per pixel), depth (2) and
+// count (1: the effective samples the other five hold; not read in a current frame).  sq, albedo and normal may be
+// nullptr.  FrameOut: the same to write.
+struct FrameView {
+  const float *sum, *sq, *albedo, *normal, *depth, *count;
+};
+struct FrameOut {
+  float *sum, *sq, *albedo, *normal, *depth, *count;
+};
+// rtw_temporal's result on the host (a triple out of use stays empty)
+struct AccumulatedFrame {
+  std::vector<float> sum, sq, albedo, normal, depth, count;
+  FrameView view() const {
+    auto p = [](const std::vector<float>& v) { return v.empty() ? nullptr : v.data(); };
+    return FrameView{p(sum), p(sq), p(albedo), p(normal), p(depth), p(count)};
+  }
+};
+// The current frame (`samples` per pixel, or d_tile_samples[tile]; rendered with cam), plus the history reprojected
+// from hist_cam onto cam with at most max_history effective samples -> out, enqueued on `stream`
+// (rtw_temporal_device).  hist = nullptr: no history.  An out buffer may be its current-frame buffer, never a history
+// buffer.
+inline void temporal_device(const FrameView& cur, uint32_t w, uint32_t h, uint32_t samples, const Camera& cam,
+                            const FrameView* hist, const Camera* hist_cam, const FrameOut& out, float max_history,
+                            float tol_z = TEMPORAL_TOL_Z, float cos_n = TEMPORAL_COS_N,
+                            const uint32_t* d_tile_samples = nullptr, int device = -1, void* stream = nullptr) {
+  const FrameView none{};
+  const FrameView& hv = hist ? *hist : none;
+  check(rtw_temporal_device(device, cur.sum, cur.sq, cur.albedo, cur.normal, cur.depth, w, h, samples, d_tile_samples,
+                            &cam.c, hv.sum, hv.sq, hv.albedo, hv.normal, hv.depth, hv.count,
+                            hist_cam ? &hist_cam->c : nullptr, max_history, tol_z, cos_n, out.sum, out.sq, out.albedo,
+                            out.normal, out.depth, out.count, stream));
+}
+// the same arithmetic over host arrays, no GPU (rtw_temporal) -> the accumulated frame
+inline AccumulatedFrame temporal(const FrameView& cur, uint32_t w, uint32_t h, uint32_t samples, const Camera& cam,
+                                 const FrameView* hist, const Camera* hist_cam, float max_history,
+                                 float tol_z = TEMPORAL_TOL_Z, float cos_n = TEMPORAL_COS_N,
+                                 const uint32_t* tile_samples = nullptr) {
+  const size_t px = (size_t)w * h;
+  AccumulatedFrame f;
+  f.sum.resize(px * 3), f.depth.resize(px * 2), f.count.resize(px);
+  if (cur.sq) f.sq.resize(px * 3);
+  if (cur.albedo) f.albedo.resize(px * 3);
+  if (cur.normal) f.normal.resize(px * 3);
+  auto p = [](std::vector<float>& v) { return v.empty() ? nullptr : v.data(); };
+  const FrameView none{};
+  const FrameView& hv = hist ? *hist : none;
+  check(rtw_temporal(cur.sum, cur.sq, cur.albedo, cur.normal, cur.depth, w, h, samples, tile_samples, &cam.c, hv.sum,
+                     hv.sq, hv.albedo, hv.normal, hv.depth, hv.count, hist_cam ? &hist_cam->c : nullptr, max_history,
+                     tol_z, cos_n, p(f.sum), p(f.sq), p(f.albedo), p(f.normal), p(f.depth), p(f.count)));
+  return f;
+}
+// The denoiser for an accumulated frame: its count per pixel in place of `samples` (rtw_denoise_counts_device; scratch
+// as denoise_device's)
+inline void denoise_counts_device(const FrameView& f, uint32_t w, uint32_t h, float* d_out, void* d_scratch,
+                                  uint32_t iterations = DENOISE_ITERATIONS, float sigma_l = DENOISE_SIGMA_L,
+                                  float sigma_n = DENOISE_SIGMA_N, float sigma_z = DENOISE_SIGMA_Z, int device = -1,
+                                  void* stream = nullptr) {
+  check(rtw_denoise_counts_device(device, f.sum, f.sq, f.albedo, f.normal, f.depth, f.count, w, h, iterations, sigma_l,
+                                  sigma_n, sigma_z, d_out, d_scratch, stream));
+}
+// the same arithmetic over host arrays, no GPU (rtw_denoise_counts) -> mean radiance, w * h * 3 floats
+inline std::vector<float> denoise_counts(const FrameView& f, uint32_t w, uint32_t h,
+                                         uint32_t iterations = DENOISE_ITERATIONS, float sigma_l = DENOISE_SIGMA_L,
+                                         float sigma_n = DENOISE_SIGMA_N, float sigma_z = DENOISE_SIGMA_Z) {
+  std::vector<float> out((size_t)w * h * 3);
+  check(rtw_denoise_counts(f.sum, f.sq, f.albedo, f.normal, f.depth, f.count, w, h, iterations, sigma_l, sigma_n,
+                           sigma_z, out.data()));
   return out;
 }
 

@@ -2,7 +2,7 @@
 //
 //   rtw_console <scene> [-w|--width 400] [-a|--aspect-ratio 1.7777778] [-s|--samples-per-pixel 100]
 //               [--seed 0] [--models models] [--out render] [--progressive STEP] [--adaptive THRESHOLD [--min-spp 16]]
-//               [--features] [--denoise [ITERATIONS]]
+//               [--features] [--denoise [ITERATIONS]] [--temporal]
 // Same Opts and defaults (main.rs:15-26), height = round(width / aspect) (:33), camera
 // aspect = width / height as f32 (:38-41), tonemap (:68-90), PNG to render/image_0000.png (:92-94).
 // --progressive (no counterpart in console_app) renders each frame through rtw_render_progressive: the PNG is rewritten
@@ -13,6 +13,9 @@
 // albedo_NNNN.png (rtw_tonemap of the albedo sums) and normal_NNNN.png (the summed normal's direction, 0.5 + 0.5 n).
 // --denoise writes, beside each frame's PNG, image_NNNN_denoised.png: the frame through rtw_denoise (the edge-avoiding
 // a-trous filter of include/rtw.h on the host arrays the render calls return, rtw.hpp's default sigmas) and rtw_tonemap.
+// --temporal renders frame k with seed + k and writes, beside each frame's PNG, image_NNNN_temporal.png: the frame
+// accumulated onto the reprojected frames before it (rtw_temporal, rtw.hpp's defaults), denoised (rtw_denoise_counts,
+// the default sigmas and --denoise's ITERATIONS) and tonemapped, all on host arrays.
 #include <ctype.h>
 #include <math.h>
 #include <stdio.h>
@@ -103,7 +106,7 @@ static void normal_rgb8(const float* n, size_t n_pixels, uint8_t* rgb) {
 int main(int argc, char** argv) {
   std::string scene, models = "models", out_dir = "render";
   uint32_t width = 400, spp = 100, step = 0, min_spp = 16;
-  bool progressive = false, adaptive = false, features = false, denoise = false;
+  bool progressive = false, adaptive = false, features = false, denoise = false, temporal = false;
   uint32_t denoise_iterations = rtw::DENOISE_ITERATIONS;
   float threshold = 0.0f;
   double aspect = 1.7777778;
@@ -127,13 +130,14 @@ int main(int argc, char** argv) {
       denoise = true;
       if (k + 1 < argc && isdigit((unsigned char)argv[k + 1][0])) denoise_iterations = (uint32_t)atoi(argv[++k]);
     }
+    else if (a == "--temporal") temporal = true;
     else if (a == "--min-spp") min_spp = (uint32_t)atoi(next("--min-spp"));
     else if (a == "-h" || a == "--help") {
       printf("usage: rtw_console <jumpy-balls|two-spheres|two-perlin-spheres|earth|simple-light|cornell-box|"
              "smokey-cornell-box|book2-final-scene|animated-book2-final-scene|simple-triangle|wavefront-cow-obj|"
              "wavefront-suspension-obj|textured-monument> [-w W] [-a ASPECT] [-s SPP] [--seed N] [--models DIR] "
              "[--out DIR] [--progressive STEP] [--adaptive THRESHOLD [--min-spp N]] [--features] "
-             "[--denoise [ITERATIONS]]\n"
+             "[--denoise [ITERATIONS]] [--temporal]\n"
              "  --progressive STEP  render each frame in growing steps (1, 2, 4, ... samples while the doubled count is\n"
              "      within STEP, then STEP at a time; 0 = doubling to the end); after every step the frame's PNG is\n"
              "      rewritten and the samples done and the mean relative standard error are printed.  That error, from\n"
@@ -152,13 +156,20 @@ int main(int argc, char** argv) {
              "  --denoise [ITERATIONS]  also write image_NNNN_denoised.png: the frame's sums, sums of squares and guides\n"
              "      through the edge-avoiding a-trous filter (rtw.h; ITERATIONS passes, default 5, at most 10; sigma_l 4,\n"
              "      sigma_n 0.5, sigma_z 0.1), on the host arrays the render calls return.  Meant for few samples (-s 4).\n"
-             "      Not with --adaptive.\n");
+             "      Not with --adaptive.\n"
+             "  --temporal  render frame k with seed N + k (one seed for every frame would repeat each pixel's noise) and\n"
+             "      also write image_NNNN_temporal.png: the frame accumulated onto the frames before it, reprojected\n"
+             "      through each pixel's mean first-hit depth onto the frame's camera (rtw.h; at most 32 SPP effective\n"
+             "      samples of history, depth within 5%%, normals within cos 0.9), then through the filter of --denoise\n"
+             "      with the accumulated sample count of each pixel.  Meant for few samples (-s 2) and a scene with\n"
+             "      several cameras (animated-book2-final-scene).  Not with --adaptive.\n");
       return 0;
     } else if (scene.empty()) scene = a;
     else { fprintf(stderr, "unexpected argument '%s'\n", a.c_str()); return 2; }
   }
   if (scene.empty()) { fprintf(stderr, "missing scene subcommand (try --help)\n"); return 2; }
   if (denoise && adaptive) { fprintf(stderr, "--denoise is not combined with --adaptive\n"); return 2; }
+  if (temporal && adaptive) { fprintf(stderr, "--temporal is not combined with --adaptive\n"); return 2; }
   const uint32_t height = (uint32_t)llround((double)width / aspect);  // main.rs:33 (f64 round)
   try {
     rtw::World world;
@@ -169,18 +180,20 @@ int main(int argc, char** argv) {
     world.commit();  // flattened and uploaded once, reused by every camera (main.rs:47-56)
     const std::vector<rtw::Camera> cams = rtw::World::preset_cameras(scene, cam_aspect, models);
     mkdir(out_dir.c_str(), 0755);
+    rtw::AccumulatedFrame history;  // --temporal: the accumulated frame before this one (empty: none yet)
+    const bool want_sq = denoise || temporal;
     for (size_t frame = 0; frame < cams.size(); ++frame) {
-      rtw::Raytracer rt(world, cams[frame], bg, width, height, spp, seed);
+      rtw::Raytracer rt(world, cams[frame], bg, width, height, spp, temporal ? seed + frame : seed);
       rtw_stats st;
       char name[32];
       snprintf(name, sizeof name, "/image_%04zu.png", frame);  // main.rs:92-94
       std::string path = out_dir + name;
       std::vector<uint8_t> img((size_t)width * height * 3);
-      std::vector<float> dn_sum, dn_sq;  // --denoise: the finished frame's sums and sums of squares
-      if (progressive || denoise) {  // (--denoise alone: the progressive call for its squares; only the last step is written)
+      std::vector<float> dn_sum, dn_sq;  // --denoise, --temporal: the finished frame's sums and sums of squares
+      if (progressive || want_sq) {  // (without --progressive: that call for its squares; only the last step is written)
         const size_t n3 = (size_t)width * height * 3;
         const int rc = rt.render_progressive([&](const float* sum, const float* sq, uint32_t done) {
-          if (denoise && done == spp) {
+          if (want_sq && done == spp) {
             dn_sum.assign(sum, sum + n3);
             dn_sq.assign(sq, sq + n3);
           }
@@ -208,7 +221,7 @@ int main(int argc, char** argv) {
         if (!write_png(path.c_str(), img.data(), width, height)) { fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
       }
       rtw::FeatureFrame ff;
-      if (features || denoise) ff = rt.render_features();
+      if (features || want_sq) ff = rt.render_features();
       if (denoise) {
         const std::vector<float> mean = rtw::denoise(dn_sum.data(), dn_sq.data(), ff.albedo.data(), ff.normal.data(),
                                                      ff.depth.data(), width, height, spp, nullptr, denoise_iterations);
@@ -216,6 +229,19 @@ int main(int argc, char** argv) {
         const std::string dpath = out_dir + name;
         rtw::check(rtw_tonemap(mean.data(), width * height, 1, img.data()));
         if (!write_png(dpath.c_str(), img.data(), width, height)) { fprintf(stderr, "cannot write %s\n", dpath.c_str()); return 1; }
+      }
+      if (temporal) {
+        const rtw::FrameView cur{dn_sum.data(), dn_sq.data(), ff.albedo.data(), ff.normal.data(), ff.depth.data(), nullptr};
+        const rtw::FrameView hist = history.view();
+        rtw::AccumulatedFrame acc = rtw::temporal(cur, width, height, spp, cams[frame], frame ? &hist : nullptr,
+                                                  frame ? &cams[frame - 1] : nullptr,
+                                                  (float)(rtw::TEMPORAL_MAX_HISTORY_FRAMES * spp));
+        const std::vector<float> mean = rtw::denoise_counts(acc.view(), width, height, denoise_iterations);
+        snprintf(name, sizeof name, "/image_%04zu_temporal.png", frame);
+        const std::string tpath = out_dir + name;
+        rtw::check(rtw_tonemap(mean.data(), width * height, 1, img.data()));
+        if (!write_png(tpath.c_str(), img.data(), width, height)) { fprintf(stderr, "cannot write %s\n", tpath.c_str()); return 1; }
+        history = std::move(acc);
       }
       if (features) {
         snprintf(name, sizeof name, "/albedo_%04zu.png", frame);

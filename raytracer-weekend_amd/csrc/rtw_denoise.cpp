@@ -1,6 +1,7 @@
 // rtw_denoise.cpp — the denoiser's C-ABI calls (include/rtw.h): rtw_denoise_scratch_bytes, rtw_denoise_device (checks,
 // then rtw_kernel.hip's enqueue_denoise) and rtw_denoise, the same arithmetic as plain loops over host arrays: what
-// rtw_tonemap is beside rtw_tonemap_device.  The filter is defined in the header operation by operation; this file and
+// rtw_tonemap is beside rtw_tonemap_device; and rtw_denoise_counts_device / rtw_denoise_counts, the same two with a
+// sample count per pixel (an accumulated frame, rtw_temporal*'s output) in place of `samples` and the tile table.  The filter is defined in the header operation by operation; this file and
 // rtw_denoise_kernel.hpp restate it independently and agree bit for bit (-ffp-contract=off, IEEE division and sqrt;
 // tests/test_denoise_abi.py holds this one to a numpy restatement, tests/test_gpu_denoise.py the kernels to both).
 #include <hip/hip_runtime.h>
@@ -44,6 +45,11 @@ int check_denoise(const void* sum, const void* out, bool scratch, uint32_t w, ui
   return RTW_OK;
 }
 
+// rtw_denoise's loops; `count` (or NULL) is rtw_denoise_counts' per-pixel sample count, which replaces n
+int denoise_host(const float* sum, const float* sq, const float* albedo, const float* normal, const float* depth,
+                 const float* count, uint32_t w, uint32_t h, uint32_t samples, const uint32_t* tile_samples,
+                 uint32_t iterations, float sigma_l, float sigma_n, float sigma_z, float* out);
+
 }  // namespace
 
 extern "C" {
@@ -66,8 +72,32 @@ int rtw_denoise_device(int device, const float* d_sum, const float* d_sq, const 
   if ((uintptr_t)d_scratch & 15u) return fail(RTW_EINVAL, "d_scratch must be 16-byte aligned");
   DeviceGuard g;
   if (device >= 0) HIPCHK(hipSetDevice(device), "hipSetDevice");
-  return enqueue_denoise(d_sum, d_sq, d_albedo, d_normal, d_depth, w, h, samples, d_tile_samples, iterations, sigma_l,
+  return enqueue_denoise(d_sum, d_sq, d_albedo, d_normal, d_depth, nullptr, w, h, samples, d_tile_samples, iterations,
+                         sigma_l, sigma_n, sigma_z, d_out, d_scratch, abi_stream(stream));
+}
+
+int rtw_denoise_counts_device(int device, const float* d_sum, const float* d_sq, const float* d_albedo,
+                              const float* d_normal, const float* d_depth, const float* d_count, uint32_t w,
+                              uint32_t h, uint32_t iterations, float sigma_l, float sigma_n, float sigma_z,
+                              float* d_out, void* d_scratch, void* stream) {
+  // (the shared checks with count among the first one's buffers and a `samples` that passes)
+  if (int e = check_denoise(d_count ? d_sum : nullptr, d_out, d_scratch != nullptr, w, h, 1, nullptr, iterations,
+                            sigma_l, sigma_n, sigma_z))
+    return e;
+  if ((uintptr_t)d_scratch & 15u) return fail(RTW_EINVAL, "d_scratch must be 16-byte aligned");
+  DeviceGuard g;
+  if (device >= 0) HIPCHK(hipSetDevice(device), "hipSetDevice");
+  return enqueue_denoise(d_sum, d_sq, d_albedo, d_normal, d_depth, d_count, w, h, 0, nullptr, iterations, sigma_l,
                          sigma_n, sigma_z, d_out, d_scratch, abi_stream(stream));
+}
+
+int rtw_denoise_counts(const float* sum, const float* sq, const float* albedo, const float* normal, const float* depth,
+                       const float* count, uint32_t w, uint32_t h, uint32_t iterations, float sigma_l, float sigma_n,
+                       float sigma_z, float* out) {
+  if (int e = check_denoise(count ? sum : nullptr, out, true, w, h, 1, nullptr, iterations, sigma_l, sigma_n, sigma_z))
+    return e;
+  return denoise_host(sum, sq, albedo, normal, depth, count, w, h, 0, nullptr, iterations, sigma_l, sigma_n, sigma_z,
+                      out);
 }
 
 int rtw_denoise(const float* sum, const float* sq, const float* albedo, const float* normal, const float* depth,
@@ -75,6 +105,17 @@ int rtw_denoise(const float* sum, const float* sq, const float* albedo, const fl
                 float sigma_l, float sigma_n, float sigma_z, float* out) {
   if (int e = check_denoise(sum, out, true, w, h, samples, tile_samples, iterations, sigma_l, sigma_n, sigma_z))
     return e;
+  return denoise_host(sum, sq, albedo, normal, depth, nullptr, w, h, samples, tile_samples, iterations, sigma_l,
+                      sigma_n, sigma_z, out);
+}
+
+}  // extern "C"
+
+namespace {
+
+int denoise_host(const float* sum, const float* sq, const float* albedo, const float* normal, const float* depth,
+                 const float* count, uint32_t w, uint32_t h, uint32_t samples, const uint32_t* tile_samples,
+                 uint32_t iterations, float sigma_l, float sigma_n, float sigma_z, float* out) {
   const size_t px = (size_t)w * h;
   const uint32_t tiles_x = (w + 7u) / 8u;
   std::vector<Rec> X, Y;
@@ -94,8 +135,9 @@ int rtw_denoise(const float* sum, const float* sq, const float* albedo, const fl
       Rec& r = X[p];
       Guide& g = G[p];
       g = Guide{{0.0f, 0.0f, 0.0f}, 0.0f};
-      live[p] = n != 0;
-      if (n == 0) {
+      const bool empty = count ? !(count[p] > 0.0f) : n == 0;  // (a NaN count is empty)
+      live[p] = !empty;
+      if (empty) {
         const uint32_t bits = 0x7FC00000u;
         float nan;
         memcpy(&nan, &bits, 4);
@@ -103,7 +145,7 @@ int rtw_denoise(const float* sum, const float* sq, const float* albedo, const fl
         D[p * 3] = D[p * 3 + 1] = D[p * 3 + 2] = 1.0f;
         continue;
       }
-      const float inv = 1.0f / (float)n;
+      const float inv = 1.0f / (count ? count[p] : (float)n);
       float m[3], d[3];
       for (int c = 0; c < 3; ++c) {
         m[c] = sum[p * 3 + c] * inv;
@@ -188,4 +230,4 @@ int rtw_denoise(const float* sum, const float* sq, const float* albedo, const fl
   return RTW_OK;
 }
 
-}  // extern "C"
+}  // namespace

@@ -29,6 +29,7 @@ struct DenoiseArgs {
   const float* normal;  // 3, or NULL
   const float* depth;   // 2, or NULL
   const uint32_t* tile_samples;  // per 8x8 tile, or NULL: `samples` everywhere
+  const float* count;   // 1 float per pixel (rtw_denoise_counts_device: it replaces n), or NULL
   uint32_t w, h, tiles_x, samples;
   float4* X;  // scratch: the iteration's input records
   float4* Y;  // scratch: its output records
@@ -54,14 +55,15 @@ __global__ __launch_bounds__(DENOISE_BLOCK) void denoise_prepare_kernel(DenoiseA
   if (i >= a.w || row >= a.h) return;
   const size_t p = (size_t)row * a.w + i;
   const uint32_t n = a.tile_samples ? a.tile_samples[(size_t)(row >> 3) * a.tiles_x + (i >> 3)] : a.samples;
-  if (n == 0u) {  // an empty pixel: never a tap (its luminance is a NaN), output +0
+  const float cnt = a.count ? a.count[p] : (float)n;
+  if (a.count ? !(cnt > 0.0f) : n == 0u) {  // an empty pixel: never a tap (its luminance is a NaN), output +0
     const float nan = __uint_as_float(0x7FC00000u);
     a.X[p] = make_float4(nan, nan, nan, 0.0f);
     a.D[p] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
     a.G[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     return;
   }
-  const float inv = 1.0f / (float)n;
+  const float inv = 1.0f / cnt;
   const float* s = a.sum + p * 3u;
   const float m0 = s[0] * inv, m1 = s[1] * inv, m2 = s[2] * inv;
   float d0 = 1.0f, d1 = 1.0f, d2 = 1.0f;

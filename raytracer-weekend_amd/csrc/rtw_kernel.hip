@@ -2,7 +2,7 @@
 // that are no templates (reduce_kernel, unpack_tiles_kernel, tile_list_kernel with its diagnostic calls, the libm and
 // reciprocal diagnostics, with the two calls that launch the latter), the tuning knobs, pick_kernel (which path-kernel variant a scene runs) and the launches
 // (enqueue_render, enqueue_render_samples, enqueue_tonemap, enqueue_tile_noise, enqueue_tonemap_tiles, enqueue_hit_rays,
-// enqueue_sample_rays, enqueue_scatter_rays, enqueue_camera_rays, enqueue_features, enqueue_denoise, enqueue_unpack),
+// enqueue_sample_rays, enqueue_scatter_rays, enqueue_camera_rays, enqueue_features, enqueue_denoise, enqueue_temporal, enqueue_unpack),
 // which share one cache of resident grids (resident_blocks), the walk's tuning (tune_walk) and the one-record-per-lane
 // queries' launch (launch_query).  The
 // scene's device copies, statistics and the render entry points are plain HIP runtime code in rtw_render.cpp, the
@@ -52,6 +52,8 @@
 // enqueue_render_samples and it is rtw_render.cpp's.
 // The denoiser (rtw_denoise_device): rtw_denoise_kernel.hpp's prepare, a-trous and finish kernels over the film's sums
 // and the feature buffers, enqueue_denoise; no scene, no device copy.
+// Temporal accumulation (rtw_temporal_device): rtw_temporal_kernel.hpp's one kernel reprojects the history's
+// accumulated sums onto the current camera and adds them to the frame's, enqueue_temporal; no scene, no scratch.
 // Variants: path_kernel<COUNT, KernelCfg K> -- one plain aggregate (stack rows, spill, waves / SIMD, feature set,
 // workgroup size, LDS node table, half nodes, 16-bit stack) is the template argument, defines every property derived
 // from it, and travels with the kernel to the host (Variant, rtw_variants.hpp), which sizes the launch from it.
@@ -74,6 +76,7 @@
 #include "rtw_shade_kernel.hpp"
 #include "rtw_film_kernel.hpp"
 #include "rtw_denoise_kernel.hpp"
+#include "rtw_temporal_kernel.hpp"
 #include "rtw_tile_beam.h"
 
 namespace rtw {
@@ -785,9 +788,9 @@ int enqueue_tonemap_tiles(const float* d_sum, uint32_t w, uint32_t h, const uint
 // RTW_DENOISE_LDS (a mask of bits 0-2) for the A/B.
 constexpr uint32_t DENOISE_LDS_STEPS = 0x3u;
 int enqueue_denoise(const float* d_sum, const float* d_sq, const float* d_albedo, const float* d_normal,
-                    const float* d_depth, uint32_t w, uint32_t h, uint32_t samples, const uint32_t* d_tile_samples,
-                    uint32_t iterations, float sigma_l, float sigma_n, float sigma_z, float* d_out, void* d_scratch,
-                    hipStream_t stream) {
+                    const float* d_depth, const float* d_count, uint32_t w, uint32_t h, uint32_t samples,
+                    const uint32_t* d_tile_samples, uint32_t iterations, float sigma_l, float sigma_n, float sigma_z,
+                    float* d_out, void* d_scratch, hipStream_t stream) {
   using namespace dev;
   const char* e = tuning_env("RTW_DENOISE_LDS");
   const uint32_t lds_steps = e ? ((uint32_t)atoi(e) & 0x7u) : DENOISE_LDS_STEPS;
@@ -797,6 +800,7 @@ int enqueue_denoise(const float* d_sum, const float* d_sq, const float* d_albedo
   memset(&a, 0, sizeof a);
   a.sum = d_sum; a.sq = d_sq; a.albedo = d_albedo; a.normal = d_normal; a.depth = d_depth;
   a.tile_samples = d_tile_samples;
+  a.count = d_count;
   a.w = w; a.h = h; a.tiles_x = (w + 7u) / 8u; a.samples = samples;
   a.X = base; a.Y = base + px; a.G = base + 2 * px; a.D = base + 3 * px;
   a.out = d_out;
@@ -824,6 +828,15 @@ int enqueue_denoise(const float* d_sum, const float* d_sq, const float* d_albedo
     HIPCHK(hipGetLastError(), "denoise_atrous_kernel launch");
     std::swap(a.X, a.Y);
   }
+  return RTW_OK;
+}
+
+// Temporal accumulation's launch: one thread per pixel, 32 x 8 pixels per workgroup as the denoiser's.
+int enqueue_temporal(const TemporalArgs& a, hipStream_t stream) {
+  using namespace dev;
+  const dim3 grid((a.w + TEMPORAL_TX - 1u) / TEMPORAL_TX, (a.h + TEMPORAL_TY - 1u) / TEMPORAL_TY), block(TEMPORAL_BLOCK);
+  hipLaunchKernelGGL(temporal_kernel, grid, block, 0, stream, a);
+  HIPCHK(hipGetLastError(), "temporal_kernel launch");
   return RTW_OK;
 }
 

@@ -290,12 +290,28 @@ int enqueue_tonemap_tiles(const float* d_sum, uint32_t w, uint32_t h, const uint
                           hipStream_t stream);
 // enqueue rtw_denoise over device arrays on `stream` of the current device: the prepare kernel, `iterations` a-trous
 // passes and the finish.  d_scratch holds DENOISE_SCRATCH_PER_PIXEL bytes per pixel, 16-byte aligned.  The caller has
-// checked the arguments (rtw_denoise_device).
+// checked the arguments (rtw_denoise_device).  d_count (or NULL): a sample count per pixel in place of `samples` and
+// the table (rtw_denoise_counts_device).
 constexpr uint64_t DENOISE_SCRATCH_PER_PIXEL = 64;
 int enqueue_denoise(const float* d_sum, const float* d_sq, const float* d_albedo, const float* d_normal,
-                    const float* d_depth, uint32_t w, uint32_t h, uint32_t samples, const uint32_t* d_tile_samples,
-                    uint32_t iterations, float sigma_l, float sigma_n, float sigma_z, float* d_out, void* d_scratch,
-                    hipStream_t stream);
+                    const float* d_depth, const float* d_count, uint32_t w, uint32_t h, uint32_t samples,
+                    const uint32_t* d_tile_samples, uint32_t iterations, float sigma_l, float sigma_n, float sigma_z,
+                    float* d_out, void* d_scratch, hipStream_t stream);
+// rtw_temporal's arguments as both of its forms take them (rtw_temporal.cpp's host loops, rtw_temporal_kernel.hpp's
+// kernel, which gets the struct by value): the current frame, the history (hist_count NULL: none) and the outputs,
+// device or host pointers alike.  A triple out of use is NULL in all three places.
+struct TemporalArgs {
+  const float *sum, *sq, *albedo, *normal, *depth;  // 3, 3, 3, 3 and 2 floats per pixel
+  const uint32_t* tile_samples;                      // per 8x8 tile, or NULL: `samples` everywhere
+  const float *hist_sum, *hist_sq, *hist_albedo, *hist_normal, *hist_depth, *hist_count;
+  float *out_sum, *out_sq, *out_albedo, *out_normal, *out_depth, *out_count;
+  uint32_t w, h, tiles_x, samples;
+  float max_history, tol_z, cos_n;
+  rtw_camera cam, hist_cam;
+};
+// enqueue rtw_temporal over device arrays on `stream` of the current device: one kernel, no scratch.  The caller has
+// checked the arguments (rtw_temporal_device).
+int enqueue_temporal(const TemporalArgs& a, hipStream_t stream);
 // enqueue one closest-hit query of n rays (rtw_ray[n] -> rtw_hit[n], device arrays) on `stream` of c.device, which
 // must be current; ev0 / ev1 (or NULL) are recorded around the kernel
 int enqueue_hit_rays(Scene& s, DeviceCopy& c, uint64_t n, const void* d_rays, void* d_hits, hipStream_t stream,
