@@ -515,9 +515,9 @@ int rtw_denoise_counts(const float* rgb_sum, const float* rgb_sq_sum, const floa
 
 /* ---- closest-hit ray queries: Hittable::hit(&ray, t_min, t_max) -> Option<HitRecord> on the world list
  *      (hittable/mod.rs:22-69) for rays the caller chooses.  A query is world.hit(ray, 0.001, +inf), the interval of
- *      lib.rs:102 and the only one the render's culling is proven for: t_min and t_max are not parameters.  The winner
- *      is the render's winner (ties go to the later object; BvhNode groups are sets), found by the path
- *      kernel's own walk for this scene. */
+ *      lib.rs:102 and the only one the render's culling is proven for: t_min and t_max are not parameters (the
+ *      occlusion queries below take a t_max).  The winner is the render's winner (ties go to the later object; BvhNode
+ *      groups are sets), found by the path kernel's own walk for this scene. */
 /* ray.rs Ray.  stream: the path RNG state at the segment start, which keys ConstantMedium's free-path sub-stream
  * (rtw_begin_constant_medium); irrelevant for worlds without media.  reserved: 0. */
 typedef struct {
@@ -557,6 +557,39 @@ int rtw_hit_rays(rtw_scene* s, int device, uint64_t n, const void* rays, void* h
  * (scene, device) must be serialised on one stream, as renders among themselves (rtw_render_device). */
 int rtw_hit_rays_device(rtw_scene* s, int device, uint64_t n, const void* d_rays, void* d_hits, void* stream,
                         rtw_stats* stats);
+
+/* ---- occlusion ray queries: world.hit(&ray, 0.001, t_max).is_some() for rays and bounds the caller chooses (shadow
+ *      rays toward a light, ambient occlusion, visibility between two points).  For ray k with bound T = t_max[k]
+ *      (+inf for every ray when t_max is NULL), let rec be the record rtw_hit_rays returns for that ray -- the same
+ *      walk, the same winner, the same `stream`-keyed media.  Then
+ *          occluded[k] = (rec.flags & RTW_HIT_HIT) && !(rec.t > T)
+ *      The bound is inclusive: the reference's primitives reject with t > t_max (spherical.rs, rectangular.rs,
+ *      triangular.rs, volumes.rs).  A hit whose t is NaN (the in-plane rect hit that only the list-mode loops report)
+ *      occludes for every T, as the reference's comparisons let a NaN pass.  T = +inf gives exactly the hit flag;
+ *      T < 0.001 gives 0 apart from that NaN case.  So the answer is the reference's world.hit(ray, 0.001, T).is_some(),
+ *      with rtw_hit_rays' own deviations only (BvhNode groups as sets).  The kernel builds no record and
+ *      does not look for the closest hit: a ray is done at the first hit within T, and boxes beyond T are culled.
+ *      A caller t_min is not offered. */
+enum {
+  RTW_OCCLUDED_HIT = 1,    /* something lies within [0.001, t_max] along the ray */
+  RTW_OCCLUDED_BAD_RAY = 2 /* time is NaN or outside the committed motion range, or t_max is NaN: not traced */
+};
+/* n rays from host memory, blocking: `rays` is rtw_ray[n] exactly as rtw_hit_rays takes it (stream keys media,
+ * reserved 0), `t_max` float[n] or NULL, `occluded` receives uint8_t[n]: 0 = free, or RTW_OCCLUDED_HIT.  Rays, bounds
+ * and answers are staged through device buffers the scene's device copy keeps, at most 2^20 rays at a time.  device -1
+ * = the first copy.  RTW_EINVAL: a NULL argument (the arrays only with n > 0, t_max never), a ray whose time is NaN or
+ * outside the committed motion range or whose t_max is NaN (a host scan before anything is enqueued; the message names
+ * the ray), or a traversal guard trip; RTW_ESTATE / RTW_ENODEV / n = 0 / degenerate rays as rtw_hit_rays.  Nothing is
+ * written beyond n bytes of `occluded`.  stats (may be NULL): rays = n, paths = 0, kernel_ms, total_ms. */
+int rtw_occluded_rays(rtw_scene* s, int device, uint64_t n, const void* rays, const float* t_max, uint8_t* occluded,
+                      rtw_stats* stats);
+/* The same from DEVICE arrays (d_rays 16-byte aligned, d_t_max 4-byte aligned or NULL) on the caller's `stream`; only
+ * enqueues unless stats != NULL; a pending guard trip is reported before it enqueues.  No host scan: a ray with a bad
+ * time or a NaN t_max comes back RTW_OCCLUDED_BAD_RAY, its neighbours unaffected.  The call uses the device copy's
+ * traversal-stack spill area: serialise it on one stream with the renders and queries of the same (scene, device), as
+ * rtw_hit_rays_device. */
+int rtw_occluded_rays_device(rtw_scene* s, int device, uint64_t n, const void* d_rays, const float* d_t_max,
+                             uint8_t* d_occluded, void* stream, rtw_stats* stats);
 
 /* ---- scatter and camera-ray queries: the other half of a caller's own integrator.  Camera::get_ray (camera.rs:66-74)
  *      and Material::scatter + Material::emitted (material.rs:23-26, light_source.rs:17-24) as batch queries over the

@@ -99,6 +99,7 @@ class rtw_sample(C.Structure):  # lib.rs:97-117 sample_ray's value for a caller'
 
 
 HIT_HIT, HIT_FRONT_FACE, HIT_BAD_RAY = 1, 2, 4
+OCCLUDED_HIT, OCCLUDED_BAD_RAY = 1, 2
 SAMPLE_END_MISS, SAMPLE_END_NO_SCATTER, SAMPLE_BAD_RAY, SAMPLE_END_DEPTH = 1, 2, 4, 8
 SAMPLE_DTYPE = np.dtype([("color", np.float32, 3), ("segments", np.uint32), ("stream", np.uint64),
                          ("flags", np.uint32), ("reserved", np.uint32)])
@@ -203,6 +204,10 @@ _SIGS = {
                                C.POINTER(rtw_stats)]),
     "rtw_hit_rays_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.POINTER(rtw_stats)]),
+    "rtw_occluded_rays": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(rtw_ray), _F, _U8,
+                                    C.POINTER(rtw_stats)]),
+    "rtw_occluded_rays_device": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.POINTER(rtw_stats)]),
     "rtw_camera_rays": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(rtw_camera), C.c_uint32, C.c_uint32, C.c_uint32,
                                   C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(rtw_ray), C.POINTER(rtw_stats)]),
     "rtw_camera_rays_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(rtw_camera), C.c_uint32, C.c_uint32,
@@ -543,6 +548,32 @@ class Scene:
         st = rtw_stats()
         _check(lib().rtw_hit_rays_device(self._p, device, n, C.c_void_p(d_rays_ptr), C.c_void_p(d_hits_ptr),
                                          C.c_void_p(stream_ptr), C.byref(st) if want_stats else None))
+        return st.as_dict() if want_stats else None
+
+    def occluded_rays(self, origin, direction, time=None, stream=None, t_max=None, device: int = 0,
+                      want_stats: bool = False):
+        """world.hit(ray, 0.001, t_max).is_some() for n rays given as hit_rays takes them, t_max [n] or None (+inf):
+        rtw_hit_rays' record with `hit and not t > t_max`, the bound inclusive, found by an any-hit walk.
+        -> a uint8 array [n]: 0 = free, OCCLUDED_HIT[, stats]."""
+        rays = make_rays(origin, direction, time, stream)
+        out = np.zeros(len(rays), np.uint8)
+        tm = None
+        if t_max is not None:
+            tm = np.ascontiguousarray(np.broadcast_to(np.asarray(t_max, np.float32), (len(rays),)))
+        st = rtw_stats()
+        _check(lib().rtw_occluded_rays(self._p, device, len(rays), rays.ctypes.data_as(C.POINTER(rtw_ray)),
+                                       tm.ctypes.data_as(_F) if tm is not None else None, out.ctypes.data_as(_U8),
+                                       C.byref(st)))
+        return (out, st.as_dict()) if want_stats else out
+
+    def occluded_rays_device(self, d_rays_ptr: int, d_t_max_ptr: int, d_out_ptr: int, n: int, device: int = 0,
+                             stream_ptr: int = 0, want_stats: bool = False):
+        """Enqueue the query of n rays in device memory (rtw_ray[n], 16-byte aligned; float[n] or 0; -> uint8[n]) on a
+        stream; waits only for stats.  A bad time or a NaN t_max comes back OCCLUDED_BAD_RAY."""
+        st = rtw_stats()
+        _check(lib().rtw_occluded_rays_device(self._p, device, n, C.c_void_p(d_rays_ptr), C.c_void_p(d_t_max_ptr or None),
+                                              C.c_void_p(d_out_ptr), C.c_void_p(stream_ptr),
+                                              C.byref(st) if want_stats else None))
         return st.as_dict() if want_stats else None
 
     def camera_rays(self, cam: "Camera", w: int, h: int, spp: int, seed: int, first: int = 0, n=None,

@@ -13,7 +13,8 @@
 //   load_wavefront_obj(path, rng)                       world.load_wavefront_obj(path)
 //   Raytracer::new(..).render() -> Pixel stream         Raytracer(..).render() -> std::vector<Pixel>
 //   world.hit(&ray, 0.001, INFINITY) -> Option<HitRecord>  world.hit_rays(rays) -> std::vector<Hit>  hittable/mod.rs:22-69
-//   cam.get_ray(u, v, rng) per path of a frame          world.camera_rays(cam, w, h, spp, seed) -> std::vector<Ray>  camera.rs:66-74
+//   world.hit(&ray, 0.001, t_max).is_some()              world.occluded_rays(rays, t_max) -> std::vector<uint8_t>
+//   cam.get_ray(u, v, rng) per path of a frame         world.camera_rays(cam, w, h, spp, seed) -> std::vector<Ray>  camera.rs:66-74
 //   rec.material.scatter(&ray, &rec, rng) / emitted()   world.scatter_rays(rays, hits, background) -> {rays, Scatter}  material.rs:23-26
 //   raytracer.sample_ray(&ray, rng, depth) -> Color      world.sample_rays(rays, background, max_depth) -> std::vector<Sample>  lib.rs:97-117
 //   (no counterpart: the frame in growing steps)        Raytracer(..).render_progressive(on_frame, step); sample_blocks; tonemap_device
@@ -191,6 +192,16 @@ class World {
     std::vector<Hit> hits(rays.size());
     check(rtw_hit_rays(s_, device, rays.size(), rays.data(), hits.data(), st));
     return hits;
+  }
+  // world.hit(&ray, 0.001, t_max[k]).is_some() for every ray, on the GPU; blocking.  t_max empty: +inf for every ray;
+  // else one bound per ray (inclusive).  -> 0 = free, RTW_OCCLUDED_HIT
+  std::vector<uint8_t> occluded_rays(const std::vector<Ray>& rays, const std::vector<float>& t_max = {},
+                                     int device = -1, rtw_stats* st = nullptr) const {
+    if (!t_max.empty() && t_max.size() != rays.size()) throw Error(RTW_EINVAL, "rays and t_max differ in length");
+    std::vector<uint8_t> occ(rays.size());
+    check(rtw_occluded_rays(s_, device, rays.size(), rays.data(), t_max.empty() ? nullptr : t_max.data(), occ.data(),
+                            st));
+    return occ;
   }
   // the render's camera rays of paths [first, first + n) of a w x h x spp frame, in rtw_render's output order
   // (lib.rs:84-86, camera.rs:66-74); n = UINT64_MAX: to the frame's end

@@ -443,10 +443,24 @@ __device__ __forceinline__ half2_t as_h2(uint32_t u) { return __builtin_bit_cast
 
 // S16: the global-node walk keeps 16-bit stack entries (the nodes' 16-bit codes, sign-extended: leaves < 0)
 // in the uint16 column `stk16`, half the LDS of the 32-bit stack (RTW_MESH_S16: more workgroups per CU)
-template <bool COUNT, int STACK, bool SPILL, uint32_t FEAT, int BLK, int NCAP, bool HN = false, bool S16 = false>
+//
+// ANY (occluded_kernel, rtw_occluded_kernel.hpp): an any-hit walk to the caller's bound `tcap` (>= TMIN, not NaN; a
+// smaller bound takes no walk at all).  The answer asked for is `best.prim >= 0 && !(best.t > tcap)` of the closest
+// hit, and every accepted candidate has t >= the closest t, so (1) a lane whose best satisfies it after a leaf phase
+// is done -- its stack is dropped -- and (2) the slab tests cull at min(best t, tcap) (RTW_OCCLUDED_CULL; DESIGN.md
+// §2: a box that holds a hit at t* <= tcap passes under any bound >= t*, and min(best, tcap) >= t*).  Best itself
+// stays unseeded: the accept's tie rule would make a seeded bound exclusive for the leaf with key 0.
+#ifndef RTW_OCCLUDED_CULL
+#define RTW_OCCLUDED_CULL 1  // 0 = early retirement alone (the ablation of DESIGN.md §4)
+#endif
+template <bool COUNT, int STACK, bool SPILL, uint32_t FEAT, int BLK, int NCAP, bool HN = false, bool S16 = false,
+          bool ANY = false>
 __device__ void trace_run(const DevScene& S, const Ray& r, TraceState& ts, int32_t* stk, int32_t* spill,
                           uint32_t spill_lanes, uint32_t* cnt, uint32_t quota, uint32_t leaf_thr, uint64_t seg,
-                          uint32_t* err, uint64_t* tph, const float4* lnodes, uint16_t* stk16) {
+                          uint32_t* err, uint64_t* tph, const float4* lnodes, uint16_t* stk16,
+                          float tcap = INFINITY) {
+  // the slab tests' far limit: the best hit's t, in an any-hit walk no farther than the caller's bound
+  auto cull_bound = [&]() { return cull_tmax((ANY && RTW_OCCLUDED_CULL) ? fminf(ts.b.t, tcap) : ts.b.t); };
   constexpr bool K16 = NCAP > 0;
   constexpr bool CODES = K16 || HN || S16;  // leaves are 16-bit codes (the 32-bit walk keeps them sign-extended)
   constexpr bool SPH_ONLY = (FEAT & (F_RECT | F_TRI | F_MEDIUM | F_INST)) == 0 && (FEAT & (F_SPHERE | F_MSPHERE));
@@ -517,7 +531,7 @@ __device__ void trace_run(const DevScene& S, const Ray& r, TraceState& ts, int32
           cnt[0]++;
           cnt[14] += (CW[0] != 0) + (CW[1] != 0) + (CW[2] != 0) + (CW[3] != 0);
         }
-        const float tmax_c = cull_tmax(ts.b.t);
+        const float tmax_c = cull_bound();
         int32_t next = -1, bk = -1;
         float best = INFINITY;
         bool hit[4];
@@ -671,7 +685,7 @@ __device__ void trace_run(const DevScene& S, const Ray& r, TraceState& ts, int32
           simd_tick(cnt, 8, 9);
           cnt[14] += (CW[0] != 0) + (CW[1] != 0) + (CW[2] != 0) + (CW[3] != 0);  // child word 0 = empty slot
         }
-        const float tmax_c = cull_tmax(ts.b.t);
+        const float tmax_c = cull_bound();
         float tn[4];
         bool hit[4];
 #pragma unroll
@@ -765,6 +779,11 @@ __device__ void trace_run(const DevScene& S, const Ray& r, TraceState& ts, int32
       ts.pend = 0;
     }
     tick(1);
+    if constexpr (ANY) {  // something within the bound: the lane has its answer
+      const bool occ = ts.b.prim >= 0 && !(ts.b.t > tcap);
+      ts.node = occ ? -1 : ts.node;
+      ts.sp = occ ? 0 : ts.sp;
+    }
     const uint64_t done = __ballot(ts.node < 0 && ts.sp == 0);
     if (done == __ballot(1) || (uint32_t)__popcll(done) >= quota) return;
   }

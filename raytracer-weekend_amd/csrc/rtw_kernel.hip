@@ -2,7 +2,7 @@
 // that are no templates (reduce_kernel, unpack_tiles_kernel, tile_list_kernel with its diagnostic calls, the libm and
 // reciprocal diagnostics, with the two calls that launch the latter), the tuning knobs, pick_kernel (which path-kernel variant a scene runs) and the launches
 // (enqueue_render, enqueue_render_samples, enqueue_tonemap, enqueue_tile_noise, enqueue_tonemap_tiles, enqueue_hit_rays,
-// enqueue_sample_rays, enqueue_scatter_rays, enqueue_camera_rays, enqueue_features, enqueue_denoise, enqueue_temporal, enqueue_unpack),
+// enqueue_occluded_rays, enqueue_sample_rays, enqueue_scatter_rays, enqueue_camera_rays, enqueue_features, enqueue_denoise, enqueue_temporal, enqueue_unpack),
 // which share one cache of resident grids (resident_blocks), the walk's tuning (tune_walk) and the one-record-per-lane
 // queries' launch (launch_query).  The
 // scene's device copies, statistics and the render entry points are plain HIP runtime code in rtw_render.cpp, the
@@ -38,6 +38,8 @@
 // its radiance to an ordered sample buffer that reduce_kernel sums per pixel in sample order.
 // Ray queries (rtw_hit_rays*): hit_kernel<K> (rtw_query_kernel.hpp) runs caller rays through the same trace_begin /
 // trace_run / hit_record under the scene's own K, one ray per lane, grid-stride; instantiated beside path_kernel<.., K>.
+// Occlusion queries (rtw_occluded_rays*): occluded_kernel<K> (rtw_occluded_kernel.hpp), hit_kernel's shape around an
+// any-hit walk to the caller's t_max (trace_run<.., ANY>), one byte per ray.
 // Radiance queries (rtw_sample_rays*): sample_kernel<K> (rtw_sample_kernel.hpp) is path_kernel's persistent loop over
 // caller rays -- index pool, ballot + mbcnt regeneration, resumable trace_run, the shading body -- without the camera,
 // the start ring and the sample buffer: one 32-byte record per ray.  Instantiated beside path_kernel<.., K> as well.
@@ -863,6 +865,32 @@ int enqueue_hit_rays(Scene& sc, DeviceCopy& c, uint64_t n, const void* d_rays, v
   a.spill = static_cast<int32_t*>(c.spill.p);
   a.err = c.err_host;
   return launch_query(var.hit, "hit_kernel launch", resident, k.blk, n, a, stream, ev0, ev1);
+}
+
+// Occlusion queries (rtw_occluded_rays*): enqueue_hit_rays' launch for the variant's occluded_kernel
+int enqueue_occluded_rays(Scene& sc, DeviceCopy& c, uint64_t n, const void* d_rays, const float* d_t_max,
+                          uint8_t* d_occluded, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+  const Knobs kn = read_knobs();
+  const Variant var = path_kernel_variant(sc.flat, kn);
+  const KernelCfg& k = var.cfg;
+  const int resident = resident_blocks(c, GRID_OCCLUDED, (const void*)var.occluded, k.blk, "occlusion kernel",
+                                       kn.verbose);
+  const WalkTuning t = tune_walk(kn, sc.flat, k, resident);
+  if (int e = grow(c.spill, (size_t)t.spill_depth * t.spill_lanes * sizeof(int32_t))) return e;
+  OccludedArgs a;
+  memset(&a, 0, sizeof a);
+  a.scene = c.scene;
+  a.rays = d_rays;
+  a.t_max = d_t_max;
+  a.occluded = d_occluded;
+  a.n = n;
+  a.time_lo = sc.flat.time_lo;
+  a.time_hi = sc.flat.time_hi;
+  a.leaf16 = t.leaf16;
+  a.spill_lanes = t.spill_lanes;
+  a.spill = static_cast<int32_t*>(c.spill.p);
+  a.err = c.err_host;
+  return launch_query(var.occluded, "occluded_kernel launch", resident, k.blk, n, a, stream, ev0, ev1);
 }
 
 // Radiance queries (rtw_sample_rays*): the scene's variant and a render's whole launch tuning (tune_launch: quota16,

@@ -1,9 +1,10 @@
-// rtw_query.cpp — the eight ray-query entry points of one device (rtw_hit_rays, rtw_sample_rays, rtw_scatter_rays,
-// rtw_camera_rays, each in a host form over host arrays and a device form over device arrays on the caller's stream)
-// and their argument checks, on one shared runtime: Query opens the scene's device copy, stages the host forms' arrays
-// chunk by chunk, and waits for and reports the device forms' statistics.  Plain HIP runtime API: the kernels and their
-// launches are rtw_kernel.hip's (enqueue_hit_rays, enqueue_sample_rays, enqueue_scatter_rays, enqueue_camera_rays); the
-// device copies, need_copy, the traversal guard's error word and the frame checks are rtw_render.cpp's.
+// rtw_query.cpp — the ten ray-query entry points of one device (rtw_hit_rays, rtw_occluded_rays, rtw_sample_rays,
+// rtw_scatter_rays, rtw_camera_rays, each in a host form over host arrays and a device form over device arrays on the
+// caller's stream) and their argument checks, on one shared runtime: Query opens the scene's device copy, stages the
+// host forms' arrays chunk by chunk, and waits for and reports the device forms' statistics.  Plain HIP runtime API:
+// the kernels and their launches are rtw_kernel.hip's (enqueue_hit_rays, enqueue_occluded_rays, enqueue_sample_rays,
+// enqueue_scatter_rays, enqueue_camera_rays); the device copies, need_copy, the traversal guard's error word and the
+// frame checks are rtw_render.cpp's.
 //
 // Every call checks in this order: a NULL argument (RTW_EINVAL), the scene's state (RTW_ESTATE; a flattened scene is
 // asked for, so that a commit that found no device answers RTW_ENODEV), for the camera calls the frame, the path range
@@ -20,17 +21,19 @@
 namespace rtw {
 namespace {
 
-// What differs between the queries beyond their arrays.  Only hit_kernel and sample_kernel walk the BVH, so only their
-// calls look at the traversal guard's error word (before anything is enqueued and after every wait) and count rays: a
-// hit query's are its n records, a radiance query's the segments its kernel counted on the device, as a render's.
+// What differs between the queries beyond their arrays.  Only hit_kernel, occluded_kernel and sample_kernel walk the
+// BVH, so only their calls look at the traversal guard's error word (before anything is enqueued and after every wait)
+// and count rays: a hit or occlusion query's are its n records, a radiance query's the segments its kernel counted on
+// the device, as a render's.
 struct Kind {
   const char* kernel;
   bool guard;    // check_guard before enqueueing and after waiting
   bool rays;     // stats->rays = n (else 0)
   bool counted;  // stats->rays = the device's segment counter (DeviceCopy::counters[0]), stats->paths = n
 };
-constexpr Kind HIT{"hit_kernel", true, true, false}, SCATTER{"scatter_kernel", false, false, false},
-    CAMERA{"camera_rays_kernel", false, false, false}, SAMPLE{"sample_kernel", true, false, true};
+constexpr Kind HIT{"hit_kernel", true, true, false}, OCCLUDED{"occluded_kernel", true, true, false},
+    SCATTER{"scatter_kernel", false, false, false}, CAMERA{"camera_rays_kernel", false, false, false},
+    SAMPLE{"sample_kernel", true, false, true};
 
 // One array of a host form: staged through `buf` in chunks, copied in from `in` and / or out to `out` (or NULL)
 struct Staged {
@@ -195,6 +198,44 @@ int rtw_hit_rays_device(rtw_scene* s, int device, uint64_t n, const void* d_rays
   if (int e = q.open(s, device, stats != nullptr)) return e;
   const hipStream_t on = abi_stream(stream);
   if (int e = enqueue_hit_rays(s->s, *q.c, n, d_rays, d_hits, on, q.e0, q.e1)) return e;
+  return q.finish_device(on, n, stats);
+}
+
+int rtw_occluded_rays(rtw_scene* s, int device, uint64_t n, const void* rays, const float* t_max, uint8_t* occluded,
+                      rtw_stats* stats) {
+  Query q(OCCLUDED);
+  if (int e = check_scene(s, n && (!rays || !occluded))) return e;
+  if (n == 0) return no_records(stats);
+  const rtw_ray* r = static_cast<const rtw_ray*>(rays);
+  const float lo = s->s.flat.time_lo, hi = s->s.flat.time_hi;
+  for (uint64_t k = 0; k < n; ++k) {
+    if (!(r[k].time >= lo && r[k].time <= hi))
+      return fail(RTW_EINVAL, "ray %llu: time %g outside the committed motion range [%g, %g]", (unsigned long long)k,
+                  r[k].time, lo, hi);
+    if (t_max && t_max[k] != t_max[k]) return fail(RTW_EINVAL, "ray %llu: t_max is NaN", (unsigned long long)k);
+  }
+  if (int e = q.open(s, device, true)) return e;
+  DeviceCopy& c = *q.c;
+  const auto enqueue = [&](uint64_t, uint64_t m) {
+    return enqueue_occluded_rays(s->s, c, m, c.qrays.p, t_max ? static_cast<const float*>(c.qtmax.p) : nullptr,
+                                 static_cast<uint8_t*>(c.qoccluded.p), nullptr, q.e0, q.e1);
+  };
+  // (without bounds the qtmax entry has nothing to copy in and grows by nothing)
+  return q.run_staged(n, stats, {{c.qrays, rays, nullptr, sizeof(rtw_ray), "hipMemcpy(rays)"},
+                                 {c.qtmax, t_max, nullptr, t_max ? sizeof(float) : 0, "hipMemcpy(t_max)"},
+                                 {c.qoccluded, nullptr, occluded, sizeof(uint8_t), "hipMemcpy(occluded)"}}, enqueue);
+}
+
+int rtw_occluded_rays_device(rtw_scene* s, int device, uint64_t n, const void* d_rays, const float* d_t_max,
+                             uint8_t* d_occluded, void* stream, rtw_stats* stats) {
+  Query q(OCCLUDED);
+  if (int e = check_scene(s, n && (!d_rays || !d_occluded))) return e;
+  if (n == 0) return no_records(stats);
+  if ((uintptr_t)d_rays & 15u) return fail(RTW_EINVAL, "d_rays must be 16-byte aligned");
+  if ((uintptr_t)d_t_max & 3u) return fail(RTW_EINVAL, "d_t_max must be 4-byte aligned");
+  if (int e = q.open(s, device, stats != nullptr)) return e;
+  const hipStream_t on = abi_stream(stream);
+  if (int e = enqueue_occluded_rays(s->s, *q.c, n, d_rays, d_t_max, d_occluded, on, q.e0, q.e1)) return e;
   return q.finish_device(on, n, stats);
 }
 

@@ -4,7 +4,8 @@
 // renders run: the list loops, the 32-bit, 16-bit (S16), half-node and LDS-node walks, the HBM stack spill, trace_far.
 //
 // A query is world.hit(ray, 0.001, +inf): lib.rs:102's interval, the only one the culling pads, the far bound and the
-// list loops' NaN rule are proven for.  Caller-chosen t_min / t_max are not offered.  The winner is the render's: ties
+// list loops' NaN rule are proven for.  Caller-chosen t_min / t_max are not offered here (occluded_kernel,
+// rtw_occluded_kernel.hpp, takes a t_max for its yes / no answer).  The winner is the render's: ties
 // to the later object, BvhNode groups as sets, the in-plane (NaN) hit reported by the list-mode loops only
 // (DESIGN.md §2).  rtw_ray::stream is the segment word that keys ConstantMedium's free-path sub-stream.
 //

@@ -123,7 +123,7 @@ void release(Scene& s) {
     if (c.err_host) hipHostFree(c.err_host);
     if (c.lists_count) hipFree(c.lists_count);
     for (DevBuf* b : {&c.sbuf, &c.spill, &c.image, &c.tiles, &c.packed, &c.gathered, &c.gather_ids, &c.qrays, &c.qhits,
-                       &c.mshade, &c.qscatter, &c.qsamples, &c.pboxes, &c.tile_lists, &c.film_sum, &c.film_sq, &c.feat_albedo, &c.feat_normal, &c.feat_depth,
+                       &c.mshade, &c.qscatter, &c.qsamples, &c.qtmax, &c.qoccluded, &c.pboxes, &c.tile_lists, &c.film_sum, &c.film_sq, &c.feat_albedo, &c.feat_normal, &c.feat_depth,
                        &c.adapt_ids, &c.adapt_tiles})
       free_buf(*b);
     if (c.adapt_host) hipHostFree(c.adapt_host);

@@ -103,7 +103,9 @@ struct ResidentGrid {
   const void* fn = nullptr;
   int blocks = 0;
 };
-enum GridSlot { GRID_PATH, GRID_PATH_COUNT, GRID_HIT, GRID_SCATTER, GRID_CAMERA, GRID_SAMPLE, GRID_FEATURE, GRID_SLOTS };
+enum GridSlot {
+  GRID_PATH, GRID_PATH_COUNT, GRID_HIT, GRID_SCATTER, GRID_CAMERA, GRID_SAMPLE, GRID_FEATURE, GRID_OCCLUDED, GRID_SLOTS
+};
 
 struct DeviceCopy {
   int device = -1;  // the logical device the caller names (rtw_render_device, rtw_render_multi's device d)
@@ -119,7 +121,7 @@ struct DeviceCopy {
   DevBuf spill;                            // traversal-stack overflow (trees deeper than the LDS stack)
   hipEvent_t kev[64][2] = {};              // pairs around path-kernel launches (ring, rtw_path_kernel_times)
   uint32_t kev_head = 0, kev_count = 0;
-  ResidentGrid grids[GRID_SLOTS];          // the path kernel (plain, counting), the four query kernels and the feature kernel
+  ResidentGrid grids[GRID_SLOTS];          // the path kernel (plain, counting), the five query kernels and the feature kernel
   // device buffers kept across render calls (grown, never shrunk; freed by release()): a
   // 30-camera animation through rtw_render does no hipMalloc after the first frame
   DevBuf image, tiles, packed, gathered, gather_ids;
@@ -133,6 +135,7 @@ struct DeviceCopy {
   DevBuf mshade;                           // Flat::mshade (uploaded with the scene; scatter_kernel's material table)
   DevBuf qscatter;                         // rtw_scatter_rays' staging: one chunk of rtw_scatter records
   DevBuf qsamples;                         // rtw_sample_rays' staging: one chunk of rtw_sample records
+  DevBuf qtmax, qoccluded;                 // rtw_occluded_rays' staging beside qrays: one chunk of bounds and of answers
   DevBuf pboxes;                           // Flat::pboxes (uploaded with the scene; tile_list_kernel's box table)
   DevBuf tile_lists;                       // one 32-B record per 8x8 tile of the last frame (tile_list_kernel)
   // the last render on this copy: 1 = its camera rays were resolved from the tile lists; tiles whose list overflowed
@@ -316,6 +319,9 @@ int enqueue_temporal(const TemporalArgs& a, hipStream_t stream);
 // must be current; ev0 / ev1 (or NULL) are recorded around the kernel
 int enqueue_hit_rays(Scene& s, DeviceCopy& c, uint64_t n, const void* d_rays, void* d_hits, hipStream_t stream,
                      hipEvent_t ev0, hipEvent_t ev1);
+// enqueue one occlusion query of n rays (rtw_ray[n], float[n] or NULL -> uint8_t[n], device arrays), likewise
+int enqueue_occluded_rays(Scene& s, DeviceCopy& c, uint64_t n, const void* d_rays, const float* d_t_max,
+                          uint8_t* d_occluded, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1);
 // enqueue Material::scatter + emitted for n (ray, hit record) pairs (device arrays; d_out_rays may be d_rays) on `stream`
 // of c.device, which must be current; ev0 / ev1 (or NULL) are recorded around the kernel
 int enqueue_scatter_rays(Scene& s, DeviceCopy& c, uint64_t n, const void* d_rays, const void* d_hits, const float* bg,
