@@ -374,6 +374,50 @@ int rtw_render_features_device(rtw_scene* s, int device, const rtw_camera* cam, 
 int rtw_render_features(rtw_scene* s, const rtw_camera* cam, const float background[3], uint32_t w, uint32_t h,
                         uint32_t spp, uint64_t seed, float* albedo, float* normal, float* depth, rtw_stats* stats);
 
+/* ---- ambient occlusion / sky visibility: per pixel, how many of the short rays cast from its first hits over the
+ *      hemisphere reach `radius` unoccluded -- a clay preview that converges at 1-4 samples, a contact-shadow guide.
+ *      No counterpart in the reference, so the buffer is DEFINED here, on the other calls' answers.  For pixel (j, i) and
+ *      sample s of a w x h frame, with ao_rays = K >= 1 and radius = R > 0:
+ *        1. The camera ray and its stream word g_0 are rtw_camera_rays' for (seed, j, i, s) (the ray
+ *           rtw_render_features* traces); rec is what rtw_hit_rays returns for it.
+ *        2. A miss adds (+0, +0) and makes no draw.
+ *        3. A hit casts K AO rays, k = 0 .. K-1 in order.  Direction d_k and next word g_{k+1}: what rtw_scatter_rays
+ *           gives as the out ray's direction and stream for rec with its material replaced by a Lambertian and the
+ *           ray's stream = g_k (rs = random_in_unit_sphere, d = normal + unit(rs), a near-zero d -> normal).  The real
+ *           material is not consulted: a light, glass or a medium casts rays the same way.  The AO ray: origin rec.p,
+ *           direction d_k (not normalised), time the camera ray's, stream g_{k+1} (it keys media as for any query).
+ *           The bound: len = sqrtf((d_x d_x + d_y d_y) + d_z d_z), T = R / len, IEEE f32, one rounding per operation
+ *           (len = 0 or R = +inf: T = +inf, plain sky visibility).  occ_k = rtw_occluded_rays' answer for that ray
+ *           and T: hit && !(t > T) on rtw_hit_rays' record (inclusive; a NaN t occludes; T < 0.001 is free but for
+ *           that case).
+ *        4. The buffer holds two floats per pixel, (open, cast), in d_depth's layout.  Per sample, in sample order:
+ *           x_0 = x_0 + (float)(K - sum of occ_k), x_1 = x_1 + (float)K; a miss adds +0 to both.  One f32 rounding per
+ *           sample, added onto what the buffer holds: zeroed buffers give a fresh frame, and samples [a, b) added onto
+ *           the sums of [0, a) are the sums of [0, b) bit for bit however the range is cut, as the colour and feature
+ *           sums.  Mean AO = open / cast (cast = 0: nothing was hit); cast / K is the pixel's hit count.
+ *      No draw beyond these.  The AO rays' walk is the scene's own any-hit walk, as rtw_occluded_rays runs it. */
+/* Samples [sample_first, sample_first + n_samples) of every pixel of the tile set, ADDED onto the DEVICE buffer d_ao
+ * (w*h*2, or packed [n_tiles][64][2]): one fused kernel in place of rtw_camera_rays_device -> rtw_hit_rays_device -> a
+ * caller's kernel making the AO rays -> rtw_occluded_rays_device and a per-pixel sum.  Tile arguments, layouts, stream,
+ * RTW_FLAG_FULL_IMAGE, what is left untouched and the serialisation rule as rtw_render_features_device (it uses the
+ * (scene, device) pair's spill area, error word and counter words).  Checks in that call's order and with its codes: a
+ * NULL argument, then a flag other than RTW_FLAG_FULL_IMAGE (both RTW_EINVAL), an uncommitted scene (RTW_ESTATE), an
+ * image under 2x2, sample_first + n_samples > 2^31, ao_rays outside 1 .. 256, a radius that is NaN or <= 0 (+inf is
+ * valid) (RTW_EINVAL), the device copy (RTW_ENODEV), then a pending traversal fault, an image side over 65536 and a
+ * camera shutter outside the committed motion range (RTW_EINVAL).  n_samples = 0 that passed the argument checks is
+ * RTW_OK and touches nothing, the device copy included.  The call only enqueues unless stats != NULL; stats: paths =
+ * the camera samples traced, rays = paths + the AO rays cast (every world.hit query), both counted on the device,
+ * kernel_ms, total_ms. */
+int rtw_render_ao_device(rtw_scene* s, int device, const rtw_camera* cam, uint32_t w, uint32_t h,
+                         uint32_t sample_first, uint32_t n_samples, uint64_t seed, uint32_t ao_rays, float radius,
+                         const uint32_t* d_tile_ids, uint32_t n_tiles, float* d_ao, void* stream, uint32_t flags,
+                         rtw_stats* stats);
+/* The host form: blocking, on the first device copy; samples [0, spp) (spp <= 2^31) of every tile summed onto a zeroed
+ * device buffer the device copy keeps and grows once, copied into ao[w*h*2] in rtw_render's layout (row r <-> j = h-1-r).
+ * spp = 0 gives zeros. */
+int rtw_render_ao(rtw_scene* s, const rtw_camera* cam, uint32_t w, uint32_t h, uint32_t spp, uint64_t seed,
+                  uint32_t ao_rays, float radius, float* ao, rtw_stats* stats);
+
 /* ---- the denoiser: an edge-avoiding a-trous wavelet filter (a dilated 5x5 B3 spline per iteration) for few-sample
  *      frames, over what the calls above leave on the device: the colour sums and sums of squares of
  *      rtw_render_samples_device / rtw_render_adaptive_device and the guides of rtw_render_features_device.  It

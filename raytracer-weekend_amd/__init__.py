@@ -185,6 +185,11 @@ _SIGS = {
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(rtw_stats)]),
     "rtw_render_features": (C.c_int, [C.c_void_p, C.POINTER(rtw_camera), _F, C.c_uint32, C.c_uint32, C.c_uint32,
                                       C.c_uint64, _F, _F, _F, C.POINTER(rtw_stats)]),
+    "rtw_render_ao_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(rtw_camera), C.c_uint32, C.c_uint32, C.c_uint32,
+                                       C.c_uint32, C.c_uint64, C.c_uint32, C.c_float, _U32, C.c_uint32, C.c_void_p,
+                                       C.c_void_p, C.c_uint32, C.POINTER(rtw_stats)]),
+    "rtw_render_ao": (C.c_int, [C.c_void_p, C.POINTER(rtw_camera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                C.c_uint32, C.c_float, _F, C.POINTER(rtw_stats)]),
     "rtw_denoise_scratch_bytes": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "rtw_denoise_device": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                      C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_float,
@@ -870,6 +875,17 @@ class Raytracer:
             C.byref(st) if want_stats else None))
         return st.as_dict() if want_stats else None
 
+    def render_ao(self, ao_rays: int = 1, radius: float = float("inf")):
+        """The ambient-occlusion buffer of this frame (rtw_render_ao; include/rtw.h defines it): per pixel the sums over
+        its spp camera rays of (open, cast) -- of the ao_rays Lambertian-distributed rays cast from each first hit, those
+        that reach `radius` unoccluded, and those cast (a miss casts none).  radius = inf: sky visibility.  Mean AO =
+        open / cast.  -> (ao[h, w, 2] in render()'s row order, stats: paths = camera samples, rays = paths + AO rays)."""
+        out = np.empty((self.h, self.w, 2), np.float32)
+        st = rtw_stats()
+        _check(lib().rtw_render_ao(self.scene._p, C.byref(self.cam.c), self.w, self.h, self.spp, self.seed, ao_rays,
+                                   radius, _fp(out), C.byref(st)))
+        return out, st.as_dict()
+
     def render_denoised(self, iterations: int = DENOISE_ITERATIONS, sigma_l: float = DENOISE_SIGMA_L,
                         sigma_n: float = DENOISE_SIGMA_N, sigma_z: float = DENOISE_SIGMA_Z, device: int = 0):
         """The frame at its spp, denoised on the device: render_samples_device with the sums of squares, then
@@ -897,6 +913,23 @@ class Raytracer:
                        iterations=iterations, sigma_l=sigma_l, sigma_n=sigma_n, sigma_z=sigma_z, device=device)
         torch.cuda.synchronize(device)
         return out.cpu().numpy().reshape(self.h, self.w, 3), st
+
+
+def render_ao_device(scene: "Scene", cam: "Camera", w: int, h: int, d_ao_ptr: int, n_samples: int, ao_rays: int = 1,
+                     radius: float = float("inf"), seed: int = 0, sample_first: int = 0, device: int = 0,
+                     d_tiles_ptr: int = 0, n_tiles: int = 0, stream_ptr: int = 0, flags: int = 0,
+                     want_stats: bool = False):
+    """rtw_render_ao_device: enqueue the ambient occlusion of samples [sample_first, sample_first + n_samples), ADDED in
+    sample order onto the device sums at d_ao_ptr (2 floats per pixel: open, cast; zeroed = a fresh frame); tiles,
+    layouts, stream and flags as Raytracer.render_features_device.  Chunks that cover [0, spp) give
+    Raytracer.render_ao()'s buffer bit for bit.  -> stats with want_stats (then the call waits), else None."""
+    st = rtw_stats()
+    _check(lib().rtw_render_ao_device(
+        scene._p, device, C.byref(cam.c), w, h, sample_first, n_samples, seed, ao_rays, radius,
+        C.cast(C.c_void_p(d_tiles_ptr), _U32) if d_tiles_ptr else None, n_tiles,
+        C.c_void_p(d_ao_ptr) if d_ao_ptr else None, C.c_void_p(stream_ptr), flags,
+        C.byref(st) if want_stats else None))
+    return st.as_dict() if want_stats else None
 
 
 def denoise_scratch_bytes(w: int, h: int) -> int:

@@ -20,6 +20,7 @@
 //   (no counterpart: the frame in growing steps)        Raytracer(..).render_progressive(on_frame, step); sample_blocks; tonemap_device
 //   (no counterpart: a sample count per 8x8 tile)       Raytracer(..).render_adaptive(threshold, min_spp) -> AdaptiveFrame; tile_noise_device; tonemap_tiles
 //   (no counterpart: a denoiser's guides)               Raytracer(..).render_features() -> FeatureFrame; render_features_device
+//   (no counterpart: ambient occlusion)                 Raytracer(..).render_ao(ao_rays, radius); render_ao_device
 //   (no counterpart: the denoiser)                       denoise_device; denoise; denoise_scratch_bytes
 //   (no counterpart: temporal accumulation)              temporal_device; temporal; denoise_counts_device; denoise_counts
 // Errors (the reference panics) throw rtw::Error with rtw_last_error()'s message.
@@ -348,6 +349,23 @@ class Raytracer {
     const float bg[3] = {bg_.x, bg_.y, bg_.z};
     check(rtw_render_features_device(world_.raw(), device, &cam_.c, bg, w_, h_, first, n, seed_, d_tile_ids, n_tiles,
                                      d_albedo, d_normal, d_depth, stream, flags, st));
+  }
+  // The ambient-occlusion buffer of this frame (rtw_render_ao): per pixel, in render_sums' order, the sums over its spp
+  // camera rays of (open, cast) -- of the ao_rays rays cast from each first hit, those unoccluded up to `radius`
+  // (INFINITY: sky visibility), and those cast; mean AO = open / cast
+  std::vector<float> render_ao(uint32_t ao_rays, float radius, rtw_stats* st = nullptr) const {
+    std::vector<float> ao((size_t)w_ * h_ * 2);
+    check(rtw_render_ao(world_.raw(), &cam_.c, w_, h_, spp_, seed_, ao_rays, radius, ao.data(), st));
+    return ao;
+  }
+  // Samples [first, first + n) of the tile set as ambient occlusion added onto the device sums d_ao (2 floats per
+  // pixel) (rtw_render_ao_device; the constructor's spp is not used); tiles, layouts and flags as
+  // render_features_device
+  void render_ao_device(int device, uint32_t first, uint32_t n, uint32_t ao_rays, float radius, float* d_ao,
+                        const uint32_t* d_tile_ids = nullptr, uint32_t n_tiles = 0, void* stream = nullptr,
+                        uint32_t flags = 0, rtw_stats* st = nullptr) const {
+    check(rtw_render_ao_device(world_.raw(), device, &cam_.c, w_, h_, first, n, seed_, ao_rays, radius, d_tile_ids,
+                               n_tiles, d_ao, stream, flags, st));
   }
 
  private:

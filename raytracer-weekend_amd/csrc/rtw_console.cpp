@@ -2,7 +2,7 @@
 //
 //   rtw_console <scene> [-w|--width 400] [-a|--aspect-ratio 1.7777778] [-s|--samples-per-pixel 100]
 //               [--seed 0] [--models models] [--out render] [--progressive STEP] [--adaptive THRESHOLD [--min-spp 16]]
-//               [--features] [--denoise [ITERATIONS]] [--temporal]
+//               [--features] [--denoise [ITERATIONS]] [--temporal] [--ao RADIUS [--ao-rays K]]
 // Same Opts and defaults (main.rs:15-26), height = round(width / aspect) (:33), camera
 // aspect = width / height as f32 (:38-41), tonemap (:68-90), PNG to render/image_0000.png (:92-94).
 // --progressive (no counterpart in console_app) renders each frame through rtw_render_progressive: the PNG is rewritten
@@ -16,6 +16,9 @@
 // --temporal renders frame k with seed + k and writes, beside each frame's PNG, image_NNNN_temporal.png: the frame
 // accumulated onto the reprojected frames before it (rtw_temporal, rtw.hpp's defaults), denoised (rtw_denoise_counts,
 // the default sigmas and --denoise's ITERATIONS) and tonemapped, all on host arrays.
+// --ao writes, beside each frame's PNG, ao_NNNN.png: the ambient occlusion of the frame's spp camera rays per pixel
+// (rtw_render_ao, K rays per hit up to RADIUS, `inf` for sky visibility) as the grey open / cast, white where nothing was
+// hit, through rtw_tonemap with spp = 1.
 #include <ctype.h>
 #include <math.h>
 #include <stdio.h>
@@ -105,8 +108,9 @@ static void normal_rgb8(const float* n, size_t n_pixels, uint8_t* rgb) {
 
 int main(int argc, char** argv) {
   std::string scene, models = "models", out_dir = "render";
-  uint32_t width = 400, spp = 100, step = 0, min_spp = 16;
-  bool progressive = false, adaptive = false, features = false, denoise = false, temporal = false;
+  uint32_t width = 400, spp = 100, step = 0, min_spp = 16, ao_rays = 1;
+  bool progressive = false, adaptive = false, features = false, denoise = false, temporal = false, ao = false;
+  float ao_radius = 0.0f;
   uint32_t denoise_iterations = rtw::DENOISE_ITERATIONS;
   float threshold = 0.0f;
   double aspect = 1.7777778;
@@ -131,13 +135,15 @@ int main(int argc, char** argv) {
       if (k + 1 < argc && isdigit((unsigned char)argv[k + 1][0])) denoise_iterations = (uint32_t)atoi(argv[++k]);
     }
     else if (a == "--temporal") temporal = true;
+    else if (a == "--ao") { ao = true; ao_radius = (float)atof(next("--ao")); }
+    else if (a == "--ao-rays") ao_rays = (uint32_t)atoi(next("--ao-rays"));
     else if (a == "--min-spp") min_spp = (uint32_t)atoi(next("--min-spp"));
     else if (a == "-h" || a == "--help") {
       printf("usage: rtw_console <jumpy-balls|two-spheres|two-perlin-spheres|earth|simple-light|cornell-box|"
              "smokey-cornell-box|book2-final-scene|animated-book2-final-scene|simple-triangle|wavefront-cow-obj|"
              "wavefront-suspension-obj|textured-monument> [-w W] [-a ASPECT] [-s SPP] [--seed N] [--models DIR] "
              "[--out DIR] [--progressive STEP] [--adaptive THRESHOLD [--min-spp N]] [--features] "
-             "[--denoise [ITERATIONS]] [--temporal]\n"
+             "[--denoise [ITERATIONS]] [--temporal] [--ao RADIUS [--ao-rays K]]\n"
              "  --progressive STEP  render each frame in growing steps (1, 2, 4, ... samples while the doubled count is\n"
              "      within STEP, then STEP at a time; 0 = doubling to the end); after every step the frame's PNG is\n"
              "      rewritten and the samples done and the mean relative standard error are printed.  That error, from\n"
@@ -162,7 +168,11 @@ int main(int argc, char** argv) {
              "      through each pixel's mean first-hit depth onto the frame's camera (rtw.h; at most 32 SPP effective\n"
              "      samples of history, depth within 5%%, normals within cos 0.9), then through the filter of --denoise\n"
              "      with the accumulated sample count of each pixel.  Meant for few samples (-s 2) and a scene with\n"
-             "      several cameras (animated-book2-final-scene).  Not with --adaptive.\n");
+             "      several cameras (animated-book2-final-scene).  Not with --adaptive.\n"
+             "  --ao RADIUS [--ao-rays K]  also write ao_NNNN.png, the frame's ambient occlusion: from the first hit of\n"
+             "      each of the pixel's SPP camera rays, K (default 1, at most 256) cosine-distributed rays; the grey value\n"
+             "      is the share of them that meet nothing within RADIUS (inf: that see the sky), white where the pixel hit\n"
+             "      nothing, through the image's tonemap.  Meant for few samples (-s 4).  Not with --adaptive.\n");
       return 0;
     } else if (scene.empty()) scene = a;
     else { fprintf(stderr, "unexpected argument '%s'\n", a.c_str()); return 2; }
@@ -170,6 +180,7 @@ int main(int argc, char** argv) {
   if (scene.empty()) { fprintf(stderr, "missing scene subcommand (try --help)\n"); return 2; }
   if (denoise && adaptive) { fprintf(stderr, "--denoise is not combined with --adaptive\n"); return 2; }
   if (temporal && adaptive) { fprintf(stderr, "--temporal is not combined with --adaptive\n"); return 2; }
+  if (ao && adaptive) { fprintf(stderr, "--ao is not combined with --adaptive\n"); return 2; }
   const uint32_t height = (uint32_t)llround((double)width / aspect);  // main.rs:33 (f64 round)
   try {
     rtw::World world;
@@ -252,6 +263,18 @@ int main(int argc, char** argv) {
         const std::string npath = out_dir + name;
         normal_rgb8(ff.normal.data(), (size_t)width * height, img.data());
         if (!write_png(npath.c_str(), img.data(), width, height)) { fprintf(stderr, "cannot write %s\n", npath.c_str()); return 1; }
+      }
+      if (ao) {
+        const std::vector<float> sums = rt.render_ao(ao_rays, ao_radius);
+        std::vector<float> grey((size_t)width * height * 3);
+        for (size_t p = 0; p < (size_t)width * height; ++p) {
+          const float open = sums[p * 2], cast = sums[p * 2 + 1];
+          grey[p * 3] = grey[p * 3 + 1] = grey[p * 3 + 2] = cast > 0.0f ? open / cast : 1.0f;
+        }
+        snprintf(name, sizeof name, "/ao_%04zu.png", frame);
+        const std::string opath = out_dir + name;
+        rtw::check(rtw_tonemap(grey.data(), width * height, 1, img.data()));
+        if (!write_png(opath.c_str(), img.data(), width, height)) { fprintf(stderr, "cannot write %s\n", opath.c_str()); return 1; }
       }
       printf("%s %ux%u %u spp: %.1f ms kernel, %llu rays, %.1f Mrays/s -> %s\n", scene.c_str(), width, height, spp,
              st.kernel_ms, (unsigned long long)st.rays, st.rays / (st.kernel_ms * 1e3), path.c_str());

@@ -1028,6 +1028,48 @@ int enqueue_features(Scene& sc, DeviceCopy& c, const Frame& f, uint32_t sample_f
   return launch_query(var.feature, "feature_kernel launch", resident, k.blk, (uint64_t)ts.n * 64u, a, stream, ev0, ev1);
 }
 
+// Ambient occlusion (rtw_render_ao*): enqueue_features' launch for the variant's ao_kernel.  The kernel adds the camera
+// samples it traced to the counters' first word and the AO rays it cast to the second.
+int enqueue_ao(Scene& sc, DeviceCopy& c, const Frame& f, uint32_t sample_first, const TileSet& ts, uint32_t ao_rays,
+               float radius, float* d_ao, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+  if (int e = check_guard(c)) return e;
+  if (int e = check_image_max(f.w, f.h)) return e;
+  if (int e = check_shutter(*f.cam, sc.flat)) return e;
+  const Knobs kn = read_knobs();
+  const Variant var = path_kernel_variant(sc.flat, kn);
+  const KernelCfg& k = var.cfg;
+  const int resident = resident_blocks(c, GRID_AO, (const void*)var.ao, k.blk, "ao kernel", kn.verbose);
+  const WalkTuning t = tune_walk(kn, sc.flat, k, resident);
+  if (int e = grow(c.spill, (size_t)t.spill_depth * t.spill_lanes * sizeof(int32_t))) return e;
+  Frame f0 = f;
+  f0.sample_base = 0;  // the key's sample word is the kernel's own s
+  const RenderArgs r = frame_args(c, f0, ts, nullptr);
+  AoArgs a;
+  memset(&a, 0, sizeof a);
+  a.scene = c.scene;
+  a.cam = r.cam;
+  a.fw1 = r.fw1; a.fh1 = r.fh1; a.rw1 = r.rw1; a.rh1 = r.rh1; a.time_span = r.time_span;
+  a.w = f.w; a.h = f.h; a.tiles_x = r.tiles_x;
+  a.n_tiles = (uint32_t)f.tiles();
+  a.seed_hash = r.seed_hash;
+  a.sample_first = sample_first;
+  a.n_samples = f.spp;
+  a.ao_rays = ao_rays;
+  a.radius = radius;
+  a.tile_ids = ts.ids;
+  a.n_slots = ts.n;
+  a.packed = r.packed_out;
+  a.ao = d_ao;
+  a.leaf16 = t.leaf16;
+  a.spill_lanes = t.spill_lanes;
+  a.spill = static_cast<int32_t*>(c.spill.p);
+  a.err = c.err_host;
+  a.counters = c.counters;
+  HIPCHK(hipMemsetAsync(c.counters, 0, COUNTER_WORDS * sizeof(unsigned long long), stream), "hipMemsetAsync");
+  // one wave per tile slot
+  return launch_query(var.ao, "ao_kernel launch", resident, k.blk, (uint64_t)ts.n * 64u, a, stream, ev0, ev1);
+}
+
 int enqueue_unpack(uint32_t w, uint32_t h, const uint32_t* d_tiles, uint32_t n_tiles, const float* d_packed,
                    float* d_image, hipStream_t stream) {
   const uint32_t n = n_tiles * 64u;

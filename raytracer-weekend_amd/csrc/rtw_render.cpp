@@ -123,7 +123,7 @@ void release(Scene& s) {
     if (c.err_host) hipHostFree(c.err_host);
     if (c.lists_count) hipFree(c.lists_count);
     for (DevBuf* b : {&c.sbuf, &c.spill, &c.image, &c.tiles, &c.packed, &c.gathered, &c.gather_ids, &c.qrays, &c.qhits,
-                       &c.mshade, &c.qscatter, &c.qsamples, &c.qtmax, &c.qoccluded, &c.pboxes, &c.tile_lists, &c.film_sum, &c.film_sq, &c.feat_albedo, &c.feat_normal, &c.feat_depth,
+                       &c.mshade, &c.qscatter, &c.qsamples, &c.qtmax, &c.qoccluded, &c.pboxes, &c.tile_lists, &c.film_sum, &c.film_sq, &c.feat_albedo, &c.feat_normal, &c.feat_depth, &c.ao_sums,
                        &c.adapt_ids, &c.adapt_tiles})
       free_buf(*b);
     if (c.adapt_host) hipHostFree(c.adapt_host);
@@ -188,6 +188,21 @@ static int check_features(const rtw_scene* s, const Frame& f, bool out, uint32_t
   if (!s || !f.cam || !f.bg || !out) return fail(RTW_EINVAL, "NULL argument");
   if (flags & ~(uint32_t)RTW_FLAG_FULL_IMAGE) return fail(RTW_EINVAL, "flags %#x: RTW_FLAG_FULL_IMAGE only", flags);
   return check_frame(s, f, out, true);
+}
+
+// the AO calls take check_features' opening with their buffer as `out`; they have no background (frame_args copies one)
+static const float AO_NO_BG[3] = {0.0f, 0.0f, 0.0f};
+// ... then, after the sample range: the AO rays per hit (the sums add (float)K exactly) and the radius (+inf is valid)
+static int check_ao(uint32_t ao_rays, float radius) {
+  if (ao_rays < 1u || ao_rays > 256u) return fail(RTW_EINVAL, "ao_rays %u: 1 .. 256", ao_rays);
+  if (!(radius > 0.0f)) return fail(RTW_EINVAL, "radius %g: must be > 0 (+inf: sky visibility)", (double)radius);
+  return RTW_OK;
+}
+// ao_kernel's two counter words as collect_stats read them (rays <- [0], node_visits <- [1]) -> the AO calls' stats
+static void ao_stats(rtw_stats& st) {
+  st.paths = st.rays;             // the camera samples traced
+  st.rays += st.node_visits;      // ... and the AO rays cast: every world.hit query
+  st.node_visits = 0;
 }
 
 // the adaptive calls' threshold: err <= threshold must be able to hold and to fail
@@ -494,6 +509,72 @@ int rtw_render_features(rtw_scene* s, const rtw_camera* cam, const float bg[3], 
   for (int k = 0; k < 3 && rc == RTW_OK; ++k)
     if (d[k] && hipMemcpy(bufs[k].host, d[k], bufs[k].bytes, hipMemcpyDeviceToHost) != hipSuccess)
       rc = fail(RTW_ENODEV, "hipMemcpy(features)");
+  st.total_ms = ms_since(t0);
+  if (stats) *stats = st;
+  return rc;
+}
+
+int rtw_render_ao_device(rtw_scene* s, int device, const rtw_camera* cam, uint32_t w, uint32_t h,
+                         uint32_t sample_first, uint32_t n_samples, uint64_t seed, uint32_t ao_rays, float radius,
+                         const uint32_t* d_tiles, uint32_t n_tiles, float* d_ao, void* stream, uint32_t flags,
+                         rtw_stats* stats) {
+  auto t0 = std::chrono::steady_clock::now();
+  const Frame f{cam, AO_NO_BG, w, h, n_samples, 1, seed};
+  if (int e = check_features(s, f, d_ao, flags)) return e;
+  if (int e = check_sample_range(sample_first, n_samples)) return e;
+  if (int e = check_ao(ao_rays, radius)) return e;
+  if (n_samples == 0) {  // nothing to add: nothing looked up, nothing enqueued
+    if (stats) *stats = rtw_stats{};
+    return RTW_OK;
+  }
+  DeviceCopy* c = need_copy(s->s, device);
+  if (!c) return RTW_ENODEV;
+  TileSet ts{d_tiles, 0, 1, d_tiles ? n_tiles : (uint32_t)f.tiles()};
+  ts.full = (flags & RTW_FLAG_FULL_IMAGE) != 0;
+  DeviceGuard g;
+  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
+  if (stats)
+    if (int e = copy_events(*c)) return e;
+  const hipEvent_t e0 = stats ? c->ev[0] : nullptr, e1 = stats ? c->ev[1] : nullptr;
+  const hipStream_t st = abi_stream(stream);
+  int rc = enqueue_ao(s->s, *c, f, sample_first, ts, ao_rays, radius, d_ao, st, e0, e1);
+  if (rc == RTW_OK && stats) {
+    rtw_stats out{};
+    rc = collect_stats(*c, st, e0, e1, 0, &out);
+    ao_stats(out);
+    out.total_ms = ms_since(t0);
+    *stats = out;
+  }
+  return rc;
+}
+
+int rtw_render_ao(rtw_scene* s, const rtw_camera* cam, uint32_t w, uint32_t h, uint32_t spp, uint64_t seed,
+                  uint32_t ao_rays, float radius, float* ao, rtw_stats* stats) {
+  auto t0 = std::chrono::steady_clock::now();
+  const Frame f{cam, AO_NO_BG, w, h, spp, 1, seed};
+  if (int e = check_features(s, f, ao, 0)) return e;
+  if (int e = check_sample_range(0, spp)) return e;
+  if (int e = check_ao(ao_rays, radius)) return e;
+  DeviceCopy* c = need_copy(s->s, -1, nullptr);
+  if (!c) return RTW_ENODEV;
+  if (int e = check_image_max(w, h)) return e;
+  DeviceGuard g;
+  HIPCHK(hipSetDevice(c->phys), "hipSetDevice");
+  if (int e = copy_events(*c)) return e;
+  const size_t bytes = (size_t)w * h * 2 * sizeof(float);
+  if (int e = grow(c->ao_sums, bytes)) return e;  // kept for the next frame, as rtw_render's image
+  float* d_ao = static_cast<float*>(c->ao_sums.p);
+  HIPCHK(hipMemsetAsync(d_ao, 0, bytes, nullptr), "hipMemsetAsync(ao)");
+  const TileSet all{nullptr, 0, 1, (uint32_t)f.tiles()};
+  rtw_stats st{};
+  int rc = RTW_OK;
+  if (spp) {
+    rc = enqueue_ao(s->s, *c, f, 0, all, ao_rays, radius, d_ao, nullptr, c->ev[0], c->ev[1]);
+    if (rc == RTW_OK) rc = collect_stats(*c, nullptr, c->ev[0], c->ev[1], 0, &st);
+    ao_stats(st);
+  }
+  if (rc == RTW_OK && hipMemcpy(ao, d_ao, bytes, hipMemcpyDeviceToHost) != hipSuccess)
+    rc = fail(RTW_ENODEV, "hipMemcpy(ao)");
   st.total_ms = ms_since(t0);
   if (stats) *stats = st;
   return rc;

@@ -104,7 +104,7 @@ struct ResidentGrid {
   int blocks = 0;
 };
 enum GridSlot {
-  GRID_PATH, GRID_PATH_COUNT, GRID_HIT, GRID_SCATTER, GRID_CAMERA, GRID_SAMPLE, GRID_FEATURE, GRID_OCCLUDED, GRID_SLOTS
+  GRID_PATH, GRID_PATH_COUNT, GRID_HIT, GRID_SCATTER, GRID_CAMERA, GRID_SAMPLE, GRID_FEATURE, GRID_OCCLUDED, GRID_AO, GRID_SLOTS
 };
 
 struct DeviceCopy {
@@ -121,11 +121,12 @@ struct DeviceCopy {
   DevBuf spill;                            // traversal-stack overflow (trees deeper than the LDS stack)
   hipEvent_t kev[64][2] = {};              // pairs around path-kernel launches (ring, rtw_path_kernel_times)
   uint32_t kev_head = 0, kev_count = 0;
-  ResidentGrid grids[GRID_SLOTS];          // the path kernel (plain, counting), the five query kernels and the feature kernel
+  ResidentGrid grids[GRID_SLOTS];          // the path kernel (plain, counting), the five query kernels, the feature and the AO kernel
   // device buffers kept across render calls (grown, never shrunk; freed by release()): a
   // 30-camera animation through rtw_render does no hipMalloc after the first frame
   DevBuf image, tiles, packed, gathered, gather_ids;
   DevBuf feat_albedo, feat_normal, feat_depth;  // rtw_render_features' device sums (grown once)
+  DevBuf ao_sums;                          // rtw_render_ao's device sums: (open, cast) per pixel (grown once)
   DevBuf film_sum, film_sq;                // rtw_render_progressive's device sums: the frame's Σ x and Σ x^2
   // rtw_render_adaptive*: two tile-id lists of the frame's tile count and the count word behind them (grown once),
   // the pinned host word the count is read back into, and the host form's per-tile counts and errors
@@ -342,6 +343,13 @@ int enqueue_sample_rays(Scene& s, DeviceCopy& c, uint64_t n, const void* d_rays,
 int enqueue_features(Scene& s, DeviceCopy& c, const Frame& f, uint32_t sample_first, const TileSet& tiles,
                      float* d_albedo, float* d_normal, float* d_depth, hipStream_t stream, hipEvent_t ev0,
                      hipEvent_t ev1);
+// enqueue samples [sample_first, sample_first + f.spp) of the tiles' pixels as ambient occlusion, ADDED in sample order
+// onto what d_ao (2 floats per pixel: open, cast) holds, on `stream` of c.device, which must be current: enqueue_features'
+// checks and counters' reset, then one launch of the scene's AO kernel (f.bg and f.max_depth unused).  Afterwards
+// c.counters[0] holds the camera samples traced and c.counters[1] the AO rays cast.  The caller has checked the range,
+// ao_rays (1 .. 256) and radius (> 0).
+int enqueue_ao(Scene& s, DeviceCopy& c, const Frame& f, uint32_t sample_first, const TileSet& tiles, uint32_t ao_rays,
+               float radius, float* d_ao, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1);
 int enqueue_unpack(uint32_t w, uint32_t h, const uint32_t* d_tiles, uint32_t n_tiles, const float* d_packed,
                    float* d_image, hipStream_t stream);
 

@@ -1,5 +1,5 @@
 // rtw_variants.hpp — the path kernel's variants as the host names them: Variant (both entry points of a
-// configuration, its ray-query, occlusion-query, radiance-query and feature-buffer kernels, and the KernelCfg the launch is sized from), make_variant, the tuning Knobs, the named configurations,
+// configuration, its ray-query, occlusion-query, radiance-query, feature-buffer and ambient-occlusion kernels, and the KernelCfg the launch is sized from), make_variant, the tuning Knobs, the named configurations,
 // and pick5, the 5-wave selection per feature set.  rtw_kernel.hip's pick_kernel instantiates every variant but the
 // F_MESHES ones, which rtw_kernel_mesh.hip's pick_mesh instantiates under its own compiler flags.
 #pragma once
@@ -10,6 +10,7 @@
 #include "rtw_occluded_kernel.hpp"
 #include "rtw_sample_kernel.hpp"
 #include "rtw_feature_kernel.hpp"
+#include "rtw_ao_kernel.hpp"
 
 namespace rtw {
 
@@ -18,6 +19,7 @@ typedef void (*hit_fn)(QueryArgs);
 typedef void (*occluded_fn)(OccludedArgs);
 typedef void (*sample_fn)(SampleArgs);
 typedef void (*feature_fn)(FeatureArgs);
+typedef void (*ao_fn)(AoArgs);
 using dev::KernelCfg;
 struct Variant {
   path_fn fn[2];  // the kernel and its COUNT build (fn[count])
@@ -25,12 +27,13 @@ struct Variant {
   occluded_fn occluded;  // the occlusion-query kernel: any hit to the caller's t_max (rtw_occluded_kernel.hpp)
   sample_fn sample;  // the radiance-query kernel: whole paths for caller rays (rtw_sample_kernel.hpp; no COUNT build)
   feature_fn feature;  // the feature-buffer kernel: first-hit albedo, normal, depth per pixel (rtw_feature_kernel.hpp)
+  ao_fn ao;  // the ambient-occlusion kernel: a closest-hit walk, then any-hit walks from the hit (rtw_ao_kernel.hpp)
   KernelCfg cfg;  // what they were compiled for: the launch (grid, stack / spill split, batch) is sized from it
 };
 template <KernelCfg K>  // the only way a Variant is made
 static Variant make_variant() {
   return {{dev::path_kernel<false, K>, dev::path_kernel<true, K>}, dev::hit_kernel<K>, dev::occluded_kernel<K>,
-          dev::sample_kernel<K>, dev::feature_kernel<K>, K};
+          dev::sample_kernel<K>, dev::feature_kernel<K>, dev::ao_kernel<K>, K};
 }
 constexpr KernelCfg with_half(KernelCfg k) { k.half = true; return k; }    // ... reading the half-precision nodes
 constexpr KernelCfg with_spill(KernelCfg k) { k.spill = true; return k; }  // ... with the HBM stack spill
